@@ -4,6 +4,11 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: bench.py re-executes itself under
                                                               torch.distributed.run -- N ranks, one GPU each, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --full                               (every block below, not just the headline)
+    python bench.py ... --dump-outputs DIR                   (DIR/latents.npy: what the last timed step returned)
+
+A plain run sets up, warms up, times the K steps and prints the headline (metric, value, unit, ms_per_step, dtype, ...);
+every other block of the line is null unless --full is given.
 
 One "step" = one classifier-free-guided DDIM step over this rank's 32 objects: a UNet forward at batch 64
 (413.5 M parameters, 3x16^3 latents, one 1280-d context token per sample) + the fused CFG/DDIM update
@@ -17,7 +22,8 @@ commonscenes_amd/synth.py) -- no checkpoints or datasets are reachable offline.
 
 Prints ONE JSON line (rank 0):
   value / ms_per_step   the metric: K timed steps between barrier + synchronize pairs, max over ranks;
-  roofline              the dominant kernel, HIP events around every one of its launches inside the timed region;
+  --full only:
+  roofline              the dominant kernel, HIP events around every one of its launches in a second pass of the K steps;
   decode                VQ-VAE decode of the rank's 32 latents (quantise + Decoder3D, 723 GFLOP/object), own roofline block;
   end_to_end            steps/s with decode + all-gather amortised over the S-step run (what a whole sample() costs);
   c2                    BASELINE configs[1]: ONE object (N=1 only): ms/step and steps/s;
@@ -85,6 +91,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--objects", type=int, default=32, help="objects per GPU (BASELINE metric: 32)")
     ap.add_argument("--ddim-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the GEMM-profiled second pass (roofline), the "
+                         "rocprofv3 --pmc child passes, decode / end-to-end / mesh / c2 / c7 / c7x5 / native-driver / "
+                         "fp32-MFMA blocks, warm conditioning and the CPU baseline; the --no-* switches below thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one returned (the latents, all ranks' objects) "
+                         "as DIR/latents.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the decode / end-to-end / C2 blocks (profiling runs)")
     ap.add_argument("--cpu-baseline", choices=["full", "quick"], default=os.environ.get("CS_CPU_BASELINE", "full"),
@@ -95,7 +108,7 @@ def parse():
                     help="no per-GEMM HIP-event hooks in the timed region (A/B runs at small batches: two event records per "
                          "GEMM launch cost ~1.3 ms of a 6.4 ms one-object step); the roofline block is then null")
     ap.add_argument("--traffic", action="store_true",
-                    help="(default at one GPU unless --no-extras / --no-traffic) measure the dominant kernel's HBM bytes per "
+                    help="(default with --full at one GPU unless --no-extras / --no-traffic) measure the dominant kernel's HBM bytes per "
                          "launch now: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of a short run of this script "
                          "(tools/pmc_traffic.sh); each pass is bounded by a timeout and a failure leaves the field null")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc passes: roofline.traffic = null")
@@ -106,7 +119,26 @@ def parse():
                          "HIP-event hooks the roofline block needs) or the native cs_unet_step driver")
     ap.add_argument("--gemm-table", action="store_true", help="print per-shape GEMM timings to stderr (debug)")
     ap.add_argument("--small", action="store_true", help="reduced-width UNet (debug only; result is not the metric)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    a.full = a.full or a.traffic or a.gemm_table      # both read the GEMM-profiled pass, which only --full runs
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """Write each array as dirpath/<name>.npy in float32; an array above DUMP_LIMIT_BYTES (all of them together) is
+    replaced by a fixed, seeded sample of its flattened elements, in their original order."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        v = t.detach().float().cpu().numpy()
+        if v.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, budget // 4, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(d / f"{name}.npy", np.ascontiguousarray(v, dtype=np.float32))
 
 
 def cpu_baseline(df, cfg, objects_per_step: int, quick: bool = False):
@@ -469,8 +501,8 @@ def main():
         return synth.gaussian_like("bench:xT", (1, 3, 16, 16, 16)).to(dev), uc_all, c_all
 
     conditioning.ssd = conditioning.nets = None
-    cond_ms = {}
-    for leg in ("cold", "warm"):        # cold = + synthetic weights, weight packing, first-launch code loading
+    cond_ms = {"warm": None}
+    for leg in ("cold", "warm") if a.full else ("cold",):   # cold = + synthetic weights, weight packing, code loading
         torch.cuda.synchronize()
         t_c = time.perf_counter()
         x_T, uc_all, c_all = conditioning()
@@ -522,9 +554,10 @@ def main():
     run(a.warmup, a.steps)
     barrier()
     dt = time.perf_counter() - t0
+    x_last = x                          # what the last timed step returned (the update writes a fresh tensor each step)
     prof = []
     dt_prof = None
-    if not a.no_gemm_profile:
+    if a.full and not a.no_gemm_profile:
         ops.GEMM_PROFILE = prof
         t0 = time.perf_counter()
         run(a.warmup + a.steps, a.steps)
@@ -540,10 +573,15 @@ def main():
     dt = max_over_ranks(dt)
     finite = bool(torch.isfinite(x).all().item())
     overflow = ops.read_status(dev) != 0
+    if a.dump_outputs:
+        lat_all = D.all_gather_objects(x_last, total)        # every rank joins the gather; rank 0 writes
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"latents": lat_all})
+        del lat_all
 
-    # ---- extras, outside the timed region: decode of this rank's latents, the all-gather, one object (C2) ----
+    # ---- extras (--full), outside the timed region: decode of this rank's latents, the all-gather, one object (C2) ----
     decode = e2e = c2 = c7 = c7x5 = mesh = fp32_leg = native = None
-    if not a.no_extras and not a.small:
+    if a.full and not a.no_extras and not a.small:
         vq = VQVAE(K.VQVAE_DDCONFIG, K.VQVAE_N_EMBED, K.VQVAE_EMBED_DIM, device=dev).set_math(a.math)
         vq.load_state_dict(synth.synth_state_dict(vqvae_param_shapes(K.VQVAE_DDCONFIG, K.VQVAE_N_EMBED,
                                                                      K.VQVAE_EMBED_DIM), device=str(dev)))
@@ -738,7 +776,7 @@ def main():
         roof["traffic_note"] = ("null: not measured in this run (PMC counters need rocprofv3 around the process; "
                                 "`bench.py --traffic` measures it in the run that prints it: profiles/r03_traffic.json is "
                                 "that measurement for this round's kernels, 562 MB per launch)")
-        want_traffic = a.traffic or not (a.no_traffic or a.no_extras or a.small)
+        want_traffic = a.full and (a.traffic or not (a.no_traffic or a.no_extras or a.small))
         # never from inside a profiler session (the child passes would inherit the outer tool's injection)
         traced = [k for k in os.environ if k.startswith(("ROCPROF", "ROCP_TOOL", "ROCTRACER")) or k == "HSA_TOOLS_LIB"]
         if traced and not a.traffic:
@@ -815,7 +853,7 @@ def main():
                        "objects_per_gpu": B, "unet_batch": 2 * B, "ddim_steps": S,
                        "parallelism": f"object-sharded x{world} (replicated weights, no per-step collective; "
                                       "1 broadcast in, 1 all-gather out)"},
-            "roofline": roof, "decode": decode, "end_to_end": e2e, "c2": c2, "c7": c7, "c7x5": c7x5, "native_driver": native, "fp32_mfma": fp32_leg,
+            "roofline": roof if a.full else None, "decode": decode, "end_to_end": e2e, "c2": c2, "c7": c7, "c7x5": c7x5, "native_driver": native, "fp32_mfma": fp32_leg,
             "mesh": mesh,
             "conditioning_ms": cond_ms["warm"], "conditioning_cold_ms": cond_ms["cold"],
             "conditioning_note": "rank 0: graph synthesis + embeddings + 5 GCN layers + rel_mlp for all objects; cold = the "
@@ -831,7 +869,7 @@ def main():
                                      else ("external launcher" if world > 1 else "single process")},
             "finite": finite, "f16x3_overflow": overflow, "unet_driver": a.driver,
         }
-        if not a.no_cpu_baseline and not a.small and world == 1:      # rank 0 at N = 1 only: the other ranks would idle
+        if a.full and not a.no_cpu_baseline and not a.small and world == 1:   # rank 0 at N = 1 only: others would idle
             res["cpu_baseline"] = cpu_baseline(df, cfg, B, quick=a.cpu_baseline == "quick")
         print(json.dumps(res), flush=True)
     if grouped:

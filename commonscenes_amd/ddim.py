@@ -74,7 +74,9 @@ class DDIMSampler(object):
         self.register_buffer("ddim_sigmas", np.asarray(sig, dtype=np.float64))
         self.register_buffer("ddim_alphas", a.numpy().astype(np.float32))
         self.register_buffer("ddim_alphas_prev", np.asarray(ap, dtype=np.float64))
-        self.register_buffer("ddim_sqrt_one_minus_alphas", torch.sqrt(1.0 - a).numpy().astype(np.float32))
+        # numpy's sqrt of the fp32 values, as the reference takes it: correctly rounded on every host (torch's CPU sqrt
+        # kernel is not on every CPU vendor)
+        self.register_buffer("ddim_sqrt_one_minus_alphas", np.sqrt((1.0 - a).numpy()).astype(np.float32))
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,

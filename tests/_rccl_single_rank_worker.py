@@ -86,7 +86,7 @@ def main():
     for k in ("MASTER_ADDR", "MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--small",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     res["bench_rc"] = r.returncode
     res["bench_tail"] = (r.stdout[-1500:] + r.stderr[-1500:]) if r.returncode else ""
     if r.returncode == 0:

@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_device():
     env = dict(os.environ, CS_BENCH_ONE_DEVICE="1", CS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29541", str(ROOT / "bench.py"), "--gpus", "2",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--objects", "4"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--objects", "4"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -38,7 +38,7 @@ def test_bench_gpus_2_without_a_launcher_spawns_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CS_BENCH_ONE_DEVICE="1", CS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--objects", "4"],
+                        "--full", "--no-cpu-baseline", "--objects", "4"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -58,7 +58,7 @@ def test_bench_eight_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CS_BENCH_ONE_DEVICE="1", CS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--small", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--objects", "2"],
+                        "--full", "--no-cpu-baseline", "--objects", "2"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
