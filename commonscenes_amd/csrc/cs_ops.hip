@@ -2,6 +2,7 @@
 // GEGLU gate, strided row copy (channel concat), row-vector add, NCDHW<->NDHWC, timestep embedding,
 // fused CFG + DDIM update, VQ nearest-code lookup, scene-graph gather / segment-mean, embedding.
 #include "cs_common.h"
+#include "cs_vq.h"
 
 namespace {
 
@@ -164,43 +165,12 @@ __global__ __launch_bounds__(256) void vq_kernel(const float* __restrict__ z, co
                                                  int64_t* __restrict__ idx, float* __restrict__ zq,
                                                  int64_t m, int ncode, int edim, int ldz, int ldq) {
   extern __shared__ __attribute__((aligned(16))) float sm[];  // [ncode][4] : e0,e1,e2|0,ee
-  for (int i = threadIdx.x; i < ncode; i += blockDim.x) {
-    float e[3] = {0.f, 0.f, 0.f};
-    float ee = 0.f;
-    for (int d = 0; d < edim && d < 3; ++d) e[d] = cb[(int64_t)i * edim + d];
-    // torch.sum(w**2, dim=1): sequential fp32 sum over edim entries
-    for (int d = 0; d < edim; ++d) {
-      const float w = cb[(int64_t)i * edim + d];
-      ee += w * w;
-    }
-    sm[4 * i + 0] = e[0];
-    sm[4 * i + 1] = e[1];
-    sm[4 * i + 2] = e[2];
-    sm[4 * i + 3] = ee;
-  }
+  cs_vq_stage_codebook(cb, sm, ncode, edim);
   __syncthreads();
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < m;
        r += (int64_t)gridDim.x * blockDim.x) {
     float zz[3] = {0.f, 0.f, 0.f};
-    float z2 = 0.f;
-    for (int d = 0; d < edim; ++d) {
-      zz[d] = z[r * ldz + d];
-      z2 += zz[d] * zz[d];
-    }
-    float best = INFINITY;
-    int bi = 0;
-    for (int i = 0; i < ncode; ++i) {
-      const float4 c = *reinterpret_cast<const float4*>(sm + 4 * i);
-      // z.e as the K=3 dot product of the reference einsum: ((z0*e0) + z1*e1) + z2*e2 via fma chain
-      float dot = zz[0] * c.x;
-      dot = fmaf(zz[1], c.y, dot);
-      dot = fmaf(zz[2], c.z, dot);
-      const float d = (z2 + c.w) - 2.0f * dot;
-      if (d < best) {
-        best = d;
-        bi = i;
-      }
-    }
+    const int bi = cs_vq_argmin(z + r * ldz, sm, ncode, edim, zz);
     idx[r] = bi;
     for (int d = 0; d < edim; ++d) zq[r * ldq + d] = cb[(int64_t)bi * edim + d];
   }

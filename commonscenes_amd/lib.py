@@ -23,6 +23,7 @@ CS_EINVAL = -22
 CS_ENOMEM = -12
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GELU, ACT_GEGLU = 0, 1, 2, 3, 4
 MATH_FP32, MATH_F16X3 = 0, 1
+VQ_ST_ROWS = 256     # CS_VQ_ST_ROWS: rows per workgroup of cs_vq_quantize_st (its scratch holds one double per tile)
 MATH_F16 = 2        # attention only: plain fp16 operands (reduced precision, opt-in)
 # The numerics mode model classes start in: F16X3 (fp32-grade, the benchmarked mode) unless CS_MATH=fp32 asks for the
 # fp32-input MFMA kernels.  `set_math()` switches per model.
@@ -191,6 +192,8 @@ SIGNATURES = {
     "cs_unet_context": (_i, [C.c_void_p, _f, _f, _i, _f, _f, _f, _l, _s]),
     "cs_unet_step": (_i, [C.c_void_p, _f, _f, _f, _f, _f, _i, _i, _f, _f, _l, _s]),
     "cs_vq_argmin_lookup": (_i, [_f, _f, _f, _f, _l, _i, _i, _i, _i, _s]),
+    "cs_vq_quantize_st": (_i, [_f, _f, _f, _f, _f, _f, _l, _i, _i, _i, _i, _i, _s]),
+    "cs_vqenc_conv_in": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _s]),
     "cs_gcn_gather_cat": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f, _s]),
     "cs_gcn_segment_mean": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _f, _s]),
     "cs_gcn_csr_ints": (_l, [_i, _i]),

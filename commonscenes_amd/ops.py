@@ -573,8 +573,13 @@ def conv_gemm(x: Tensor, w: PackedWeight, *, spatial: Optional[Tuple[int, int, i
               scale: Optional[Tensor] = None, shift: Optional[Tensor] = None,
               out: Optional[Tensor] = None, tile: int = 0, math: int = L.MATH_FP32,
               splitk: Optional[int] = None, out_fn=None, a_scale: Optional[float] = None,
-              stats: bool = False, out_pair: Optional[float] = None, x_bound: Optional[Tensor] = None):
+              stats: bool = False, out_pair: Optional[float] = None, x_bound: Optional[Tensor] = None,
+              pad: Optional[Sequence] = None):
     """Conv3d (k in {1,3}, pad k//2) / Linear.  x: [nb,d,h,w,c] (conv) or [..., c] rows (linear).
+
+    `pad=(pd, ph, pw)`: explicit pads per dim instead of k//2, each an int or a (low, high) pair; the output extent is
+    (v + low + high - k) // stride + 1 and taps beyond the input read zero -- e.g. the VQ encoder's Downsample,
+    F.pad(x, (0, 1, 0, 1, 0, 1)) + Conv3d(stride 2, pad 0), is pad=((0, 1),) * 3, stride=(2, 2, 2).
 
     `spatial=(nb,d,h,w)` lets a row matrix be interpreted as a volume without reshaping.
     r4: `stats=True` -- the result feeds a GroupNorm: where the launch can (cs_conv_gemm_epilogue_caps), its epilogue
@@ -586,11 +591,11 @@ def conv_gemm(x: Tensor, w: PackedWeight, *, spatial: Optional[Tuple[int, int, i
     """
     if w.tapcol is not None:
         if (tuple(stride) != (1, 1, 1) or tuple(up) != (0, 0, 0) or act != L.ACT_NONE or rowvec is not None
-                or res is not None or scale is not None or tile or splitk):
+                or res is not None or scale is not None or tile or splitk or pad is not None):
             raise L.CsError("taps-as-columns weights: plain 3x3x3 conv only (no stride / up / act / residual / tile)")
         return _conv_tapcol(x, w, spatial, a_scale, out, out_fn)
     if isinstance(x, Wino16):
-        if tuple(stride) != (1, 1, 1) or tuple(up) != (0, 0, 0) or tile or splitk or x_bound is not None:
+        if tuple(stride) != (1, 1, 1) or tuple(up) != (0, 0, 0) or tile or splitk or x_bound is not None or pad is not None:
             raise L.CsError("a Wino16 activation feeds a plain 3x3x3 stride-1 conv (no stride / up / tile / splitk)")
         return _conv_wino(x, w, act, rowvec, rv_rows, res, scale, shift, out, out_fn, stats, out_pair)
     xs = xp = None
@@ -623,11 +628,19 @@ def conv_gemm(x: Tensor, w: PackedWeight, *, spatial: Optional[Tuple[int, int, i
         nb, d, h, wd = spatial
         if nb * d * h * wd != m:
             raise L.CsError("spatial does not match x rows")
-    pd, ph, pw = kd // 2, kh // 2, kw // 2
+    if pad is None:
+        pd, ph, pw = kd // 2, kh // 2, kw // 2
+        qd, qh, qw = pd, ph, pw
+    else:
+        if len(pad) != 3 or w.classes is not None:
+            raise L.CsError("pad: three per-dim entries; not with a folded Upsample weight")
+        (pd, qd), (ph, qh), (pw, qw) = ((int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1])) for v in pad)
+        if min(pd, ph, pw, qd, qh, qw) < 0:
+            raise L.CsError("pad: negative pads")
     vd, vh, vw = d << up[0], h << up[1], wd << up[2]
-    do = (vd + 2 * pd - kd) // stride[0] + 1
-    ho = (vh + 2 * ph - kh) // stride[1] + 1
-    wo = (vw + 2 * pw - kw) // stride[2] + 1
+    do = (vd + pd + qd - kd) // stride[0] + 1
+    ho = (vh + ph + qh - kh) // stride[1] + 1
+    wo = (vw + pw + qw - kw) // stride[2] + 1
     mo = nb * do * ho * wo
     ocols = w.cout // 2 if act == L.ACT_GEGLU else w.cout
     if out is None:
@@ -1411,6 +1424,49 @@ def vq_lookup(z: Tensor, codebook: Tensor) -> Tuple[Tensor, Tensor]:
                                          zq.data_ptr(), m, ncode, edim, ldz, ldq, _stream()),
             "cs_vq_argmin_lookup")
     return idx, zq
+
+
+def vq_quantize_st(z: Tensor, codebook: Tensor, nb: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """VectorQuantizer.forward's encode outputs over nb objects of equal row count: z [..., ld>=edim] rows -> (idx int64
+    [M], zst = z + (z_q - z) [..., ld] (columns past edim zero), per-object fp64 sums of (z_q - z)^2 [nb])."""
+    _chk(z, "z"); _chk(codebook, "codebook")
+    m, c, ldz = rows_ld(z, "z")
+    ncode, edim = codebook.shape
+    if nb <= 0 or m % nb:
+        raise L.CsError(f"vq_quantize_st: {m} rows do not split into {nb} objects")
+    rows = m // nb
+    idx = torch.empty((m,), dtype=torch.int64, device=z.device)
+    zst = torch.zeros(z.shape, dtype=torch.float32, device=z.device)
+    _, _, ldq = rows_ld(zst, "zst")
+    tiles = (rows + L.VQ_ST_ROWS - 1) // L.VQ_ST_ROWS
+    part = torch.empty((nb * tiles,), dtype=torch.float64, device=z.device)
+    loss = torch.empty((nb,), dtype=torch.float64, device=z.device)
+    L.check(L.load().cs_vq_quantize_st(z.data_ptr(), codebook.contiguous().data_ptr(), idx.data_ptr(), zst.data_ptr(),
+                                       part.data_ptr(), loss.data_ptr(), rows, nb, ncode, edim, ldz, ldq, _stream()),
+            "cs_vq_quantize_st")
+    return idx, zst, loss
+
+
+def vqenc_conv_in(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The VQ encoder's first conv, Conv3d(1 -> cout, 3x3x3, pad 1): x [nb, 1, d, h, w] (NCDHW) -> [nb, d, h, w, cout]."""
+    _chk(x, "x"); _chk(w, "weight")
+    if x.dim() != 5 or x.shape[1] != 1 or w.dim() != 5 or tuple(w.shape[1:]) != (1, 3, 3, 3):
+        raise L.CsError("vqenc_conv_in: x [nb, 1, d, h, w] and w [cout, 1, 3, 3, 3] expected")
+    x = x.contiguous()
+    nb, _, d, h, wd = (int(v) for v in x.shape)
+    cout = int(w.shape[0])
+    if out is None:
+        out = torch.empty((nb, d, h, wd, cout), dtype=torch.float32, device=x.device)
+    _chk(out, "out")
+    om, oc, ldo = rows_ld(out, "out")
+    if om != nb * d * h * wd or oc != cout:
+        raise L.CsError(f"out has shape {tuple(out.shape)}, expected {nb * d * h * wd} rows x {cout}")
+    if bias is not None:
+        _chk(bias, "bias")
+        bias = bias.contiguous()
+    L.check(L.load().cs_vqenc_conv_in(x.data_ptr(), w.contiguous().data_ptr(), _ptr(bias), out.data_ptr(), nb, d, h, wd,
+                                      cout, ldo, _stream()), "cs_vqenc_conv_in")
+    return out
 
 
 def gcn_gather_cat(obj: Tensor, pred: Tensor, edges: Tensor) -> Tensor:

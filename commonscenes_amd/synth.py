@@ -161,3 +161,19 @@ def random_scene_graph(n_objects: int, seed: int = 111, n_obj_classes: int = 35,
     return dict(objs=torch.from_numpy(objs), triples=torch.from_numpy(triples),
                 text_feats=clip_like("text", O), rel_feats=clip_like("rel", T),
                 z=gaussian_like("graph:z", (O, 64), seed))
+
+
+def sdf_volume(variant: int = 0, res: int = 64) -> torch.Tensor:
+    """An analytic SDF-like volume [1, 1, res, res, res] (fp32): the signed distance to the union of a sphere and a box
+    on the cube [-1, 1]^3, clipped to +-0.2 like the truncated SDFs SDFusion encodes.  Every float64 operation is exact
+    or a single correctly-rounded IEEE op, so the result is platform independent."""
+    c = (np.arange(res, dtype=np.float64) + 0.5) * (2.0 / res) - 1.0
+    z, y, x = np.meshgrid(c, c, c, indexing="ij")
+    (sc, sr), (bc, bh) = [(((0.1, -0.05, 0.0), 0.5), ((-0.2, 0.1, 0.1), (0.3, 0.2, 0.4))),
+                          (((-0.15, 0.2, 0.05), 0.35), ((0.15, -0.1, -0.05), (0.45, 0.15, 0.3)))][variant % 2]
+    ds = np.sqrt((x - sc[0]) ** 2 + (y - sc[1]) ** 2 + (z - sc[2]) ** 2) - sr
+    q = [np.abs(v - o) - h for v, o, h in zip((x, y, z), bc, bh)]
+    outside = np.sqrt(np.maximum(q[0], 0.0) ** 2 + np.maximum(q[1], 0.0) ** 2 + np.maximum(q[2], 0.0) ** 2)
+    db = outside + np.minimum(np.maximum(q[0], np.maximum(q[1], q[2])), 0.0)
+    d = np.clip(np.minimum(ds, db), -0.2, 0.2)
+    return torch.from_numpy(d.astype(np.float32).reshape(1, 1, res, res, res))

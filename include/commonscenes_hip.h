@@ -629,6 +629,28 @@ int cs_vq_argmin_lookup(const float* z, const float* codebook, int64_t* idx, flo
                         int ncode, int edim, int ldz, int ldq, cs_stream_t stream);
 
 /*
+ * VQ quantiser with the reference's encode outputs (quantizer.py:68-119, legacy=False): nb objects of `rows` rows each,
+ * z [nb*rows][ldz] (first edim entries), codebook [ncode][edim] ->
+ *   idx[nb*rows]        the nearest code: the same search and tie rule as cs_vq_argmin_lookup, bit for bit
+ *   zst[nb*rows][ldq]   the straight-through value z + (z_q - z) in fp32 (may differ from the code row by an ulp)
+ *   loss[nb]            per object, the fp64 sum of (z_q - z)^2 (difference in fp32) in a fixed order: workgroups of
+ *                       CS_VQ_ST_ROWS rows, then their partials in row order -- no atomics, independent of nb
+ * part: caller scratch of nb * ceil(rows / CS_VQ_ST_ROWS) doubles.  edim <= 3.
+ */
+#define CS_VQ_ST_ROWS 256
+int cs_vq_quantize_st(const float* z, const float* codebook, int64_t* idx, float* zst, double* part, double* loss,
+                      int64_t rows, int nb, int ncode, int edim, int ldz, int ldq, cs_stream_t stream);
+
+/*
+ * VQ-VAE Encoder3D.conv_in (vqvae_modules.py:201-205): Conv3d(1 -> cout, 3x3x3, stride 1, pad 1) on the raw SDF.
+ * x [nb][d][h][w] (NCDHW with C = 1 is already channels-last), w [cout][1][3][3][3], bias [cout] (may be NULL) ->
+ * out [nb*d*h*w][ldo] channels-last, 16-byte aligned.  fp32 FMAs over the 27 taps in (kd, kh, kw) order, then + bias:
+ * one result whatever the GEMM numerics mode.  cout % 4 == 0, cout <= 256.
+ */
+int cs_vqenc_conv_in(const float* x, const float* w, const float* bias, float* out, int nb, int d, int h, int wd,
+                     int cout, int ldo, cs_stream_t stream);
+
+/*
  * Scene-graph convolution helpers (model/graph.py:146-151,176-199).
  *   cs_gcn_gather_cat:   out[t] = [obj[s_t] | pred[t] | obj[o_t]],  edges [t][2] int64
  *   cs_gcn_segment_mean: pooled[i] = (sum_{t: s_t = i} new_t[0:h] (edge order) then

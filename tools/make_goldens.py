@@ -8,7 +8,7 @@ monkeypatches (reference files untouched), load deterministic synthetic weights
 dump small input/output fixtures.  The fixtures are DATA (inputs + expected outputs); nothing of
 the reference's source is copied.
 
-    python tools/make_goldens.py [--only NAME ...]
+    python tools/make_goldens.py [--only NAME ...]          (e.g. --only vq_encode)
 """
 from __future__ import annotations
 
@@ -18,6 +18,7 @@ import sys
 import tempfile
 import time
 import types
+from collections import OrderedDict
 from pathlib import Path
 from unittest import mock
 
@@ -343,6 +344,46 @@ def g_vq():
          latent_nq=h[:, :, :8, :8, :8].contiguous(), dec_nq=dec_nq)
 
 
+def build_ref_vqvae_full():
+    """The reference VQVAE with synthetic weights on BOTH sides (the decoder's values are those of build_ref_vqvae:
+    synth is keyed by name)."""
+    from model.networks.vqvae_networks.network import VQVAE
+    from commonscenes_amd.vqvae import vqvae_encoder_param_shapes, vqvae_param_shapes
+    mp = vq_conf().model.params
+    vq = VQVAE(mp.ddconfig, mp.n_embed, mp.embed_dim).eval()
+    dshapes = vqvae_param_shapes(dict(mp.ddconfig), mp.n_embed, mp.embed_dim)
+    eshapes = vqvae_encoder_param_shapes(dict(mp.ddconfig), mp.n_embed, mp.embed_dim)
+    ref = [(k, tuple(v.shape)) for k, v in vq.state_dict().items()]
+    assert [kv for kv in ref if kv[0] in eshapes] == list(eshapes.items()), \
+        "vqvae_encoder_param_shapes disagrees with the reference state_dict (names, shapes or order)"
+    assert set(dict(ref)) == set(dshapes) | set(eshapes)
+    sd = synth.synth_state_dict(OrderedDict(list(eshapes.items()) + list(dshapes.items())))
+    vq.load_state_dict(sd, strict=True)
+    return vq, sd
+
+
+def g_vq_encode():
+    """VQVAE.encode_no_quant / encode / forward on two analytic SDF volumes (synth.sdf_volume: the tests rebuild the
+    input, so only its checksum is stored).  dec is kept as a 32^3 corner crop plus the full volume's fp64 norm (the
+    whole 64^3 output would not fit the fixture size limit)."""
+    vq, sd = build_ref_vqvae_full()
+    x = torch.cat([synth.sdf_volume(0), synth.sdf_volume(1)], dim=0)
+    with torch.no_grad():
+        t0 = time.time()
+        h = vq.encode_no_quant(x)
+        print(f"[vq_encode] reference encode_no_quant {time.time() - t0:.1f}s")
+        quant, emb_loss, info = vq.encode(x)
+        t0 = time.time()
+        dec, diff = vq(x)
+        print(f"[vq_encode] reference forward {time.time() - t0:.1f}s")
+        z2 = vq(x, forward_no_quant=True, encode_only=True)
+    assert torch.equal(z2, h) and torch.equal(diff, emb_loss)
+    save("vq_encode", x_sum=np.float64(x.double().sum()), x_abs_sum=np.float64(x.double().abs().sum()),
+         h=h, quant=quant, indices=info[2], emb_loss=emb_loss.reshape(1),
+         dec_crop=dec[:, :, :32, :32, :32].contiguous(), dec_norm=np.float64(dec.double().norm()),
+         dec_sum=np.float64(dec.double().sum()))
+
+
 def _scene_yaml(tmp: Path, small: bool, vq_ckpt: Path, concat: bool = False) -> Path:
     with open(REF / "config" / ("v2_full_concat.yaml" if concat else "v2_full.yaml")) as f:
         y = yaml.safe_load(f)
@@ -636,7 +677,7 @@ def main():
     install_patches()
     todo = a.only or ["schedule", "unet_small", "unet_full", "ddim_small", "ddim_full", "vq", "gcn", "e2e",
                       "unet_concat_small", "unet_concat_full", "ddim_concat_small", "gcn_concat", "e2e_concat", "box",
-                      "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full"]
+                      "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode"]
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name in todo:
@@ -653,6 +694,8 @@ def main():
                 g_ddim(False)
             elif name == "vq":
                 g_vq()
+            elif name == "vq_encode":
+                g_vq_encode()
             elif name == "gcn":
                 g_gcn(tmp)
             elif name == "e2e":
