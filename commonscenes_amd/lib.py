@@ -174,6 +174,9 @@ SIGNATURES = {
     "cs_emd_approxmatch": (_i, [_f, _f, _f, _f, _i, _i, _i, _s]),
     "cs_emd_matchcost": (_i, [_f, _f, _f, _f, _i, _i, _i, _s]),
     "cs_emd_matchcost_grad": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _s]),
+    "cs_chamfer_pairwise": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
+    "cs_emd_pairwise_cost": (_i, [_f, _f, _f, _i, _i, _i, _i, _s]),
+    "cs_occupancy_histogram": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _s]),
     "cs_mc_blocks_per_object": (_i, [_i]),
     "cs_mc_count": (_i, [_f, _i, _i, _fl, _i, _f, _s]),
     "cs_mc_emit": (_i, [_f, _i, _i, _fl, _i, _f, _f, _f, _f, _f, _f, _fl, _fl, _s]),

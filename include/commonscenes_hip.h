@@ -728,6 +728,36 @@ int cs_emd_matchcost_grad(const float* xyz1, const float* xyz2, const float* mat
                           int n, int m, cs_stream_t stream);
 
 /*
+ * All-pairs metric matrices: what scripts/compute_mmd_cov_1nn.py builds by copying one cloud batch_size times and looping on
+ * the host (_pairwise_EMD_CD_, :110-150), here one workgroup per pair, no cloud copied, forward only.
+ *
+ * cs_chamfer_pairwise: out[i][j] = mean_k min_l |a_ik - b_jl|^2 + mean_l min_k |a_ik - b_jl|^2 (:131-134 on the output of
+ *   nn_distance) for a [na][p][3], b [nb][q][3]; out [na][nb] fp32.  Distances are ((dx*dx + dy*dy) + dz*dz) of differences,
+ *   as in cs_chamfer_nm_distance, each formed once for both directions; the means are fixed-order sums, so out[i][j] does
+ *   not depend on na, nb or the pair's place in the launch, and two runs agree bit for bit.  symmetric != 0 (a == b,
+ *   na == nb, p == q required) computes i <= j and mirrors: bit-equal to the full matrix.  q <= CS_CHAMFER_PAIRWISE_MAX_Q.
+ *
+ * cs_emd_pairwise_cost: cost[i][j] = cs_emd_matchcost of cs_emd_approxmatch(a_i, b_j) (match_cost.py:45 as :56-62 calls it;
+ *   the caller divides by the point count) for a [na][n][3], b [nb][m][3]; cost [na][nb] fp32.  The same nine levels,
+ *   guards, fast exponential and in-order sums as cs_emd_approxmatch, but the match matrix is never formed: pass 3 adds
+ *   w |d| to a per-row cost.  The result differs from the two-call route in summation order only.  No workspace.
+ *   n, m <= CS_EMD_PAIRWISE_MAX_POINTS (the rows a 1024-thread workgroup holds in registers); larger clouds take the
+ *   per-pass entries above.
+ *
+ * cs_occupancy_histogram: entropy_of_occupancy_grid's counters (:287-300) for clouds [s][p][3] over ONE grid [g][3]:
+ *   idx [s][p] = each point's nearest cell (ties: lowest index), counters [g] = hits, bernoulli [g] = clouds with at least
+ *   one hit; both zeroed here.  g <= CS_OCCUPANCY_MAX_CELLS.
+ */
+#define CS_CHAMFER_PAIRWISE_MAX_Q 32768
+#define CS_EMD_PAIRWISE_MAX_POINTS 8192
+#define CS_OCCUPANCY_MAX_CELLS 524288
+int cs_chamfer_pairwise(const float* a, const float* b, float* out, int na, int nb, int p, int q, int symmetric,
+                        cs_stream_t stream);
+int cs_emd_pairwise_cost(const float* a, const float* b, float* cost, int na, int nb, int n, int m, cs_stream_t stream);
+int cs_occupancy_histogram(const float* clouds, const float* grid, int32_t* idx, int32_t* counters, int32_t* bernoulli,
+                           int s, int p, int g, cs_stream_t stream);
+
+/*
  * SDF -> triangle mesh by marching cubes (model/diff_utils/util_3d.py:194-236 sdf_to_mesh, which runs
  * PyMCubes' mcubes.marching_cubes(sdf_i, level) on the CPU per object).  sdf: [nb][n][n][n] fp32 (the decoder's
  * (B,1,64,64,64) output as is), n <= 160.  A vertex per grid edge whose endpoints straddle `level` ((v < level) differs),

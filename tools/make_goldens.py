@@ -566,7 +566,7 @@ def g_full_manip(tmp: Path):
     z = synth.gaussian_like("fm:z", (O, 64))
     z_in = torch.cat([z[:2], z[3:]], dim=0)
     x_T = synth.gaussian_like("fm:xT", (1, 3, 16, 16, 16))
-    model.Diff.rel2shape = functools.partial(model.Diff.rel2shape, ddim_steps=steps)
+    model.Diff.rel2shape = functools.partial(model.Diff.rel2shape, ddim_steps=2)
     idx_rec = _record_vq_indices(model.Diff.vqvae_module)
     lat = []
     dnq = model.Diff.vqvae_module.decode_no_quant
@@ -669,6 +669,108 @@ def g_plms():
          x=torch.stack([xi[k] for k in TRAJ_KEEP]), pred_x0_final=inter["pred_x0"][-1])
 
 
+def _shape_clouds(rng, count, points, kind_bias):
+    """noisy surface samples of parametrised boxes / ellipsoids, centred and scaled like the script's `normalization`"""
+    import scripts.compute_mmd_cov_1nn as R
+    out = []
+    for _ in range(count):
+        half = rng.uniform(0.25, 1.0, 3)
+        if rng.uniform() < kind_bias:                                        # ellipsoid surface
+            v = rng.normal(size=(points, 3))
+            pc = v / np.linalg.norm(v, axis=1, keepdims=True) * half
+        else:                                                                # box surface: one coordinate pinned to a face
+            pc = rng.uniform(-1.0, 1.0, (points, 3))
+            face = rng.integers(0, 3, points)
+            pc[np.arange(points), face] = rng.choice([-1.0, 1.0], points)
+            pc = pc * half
+        pc = pc + rng.normal(scale=0.01, size=pc.shape)
+        out.append(R.normalization(pc.copy()))
+    return np.stack(out).astype(np.float32)
+
+
+def _min_gap(m, axis):
+    """smallest relative gap between the minimum and the runner-up along `axis`"""
+    s = np.sort(m, axis=axis)
+    first, second = np.take(s, 0, axis=axis), np.take(s, 1, axis=axis)
+    return float(((second - first) / second).min())
+
+
+def _knn_joint(xx, xy, yy):
+    m = np.block([[xx, xy], [xy.T, yy]])
+    return m + np.diag(np.full(len(m), np.inf))
+
+
+def g_shape_metrics():
+    """tests/golden/shape_metrics.npz: two sets of 24 clouds x 256 points and what scripts/compute_mmd_cov_1nn.py computes
+    from them on the CPU in float64 (its torch Chamfer and its Hungarian EMD: the CUDA extensions are absent, so the
+    script's own fallbacks run).  The conditions the tests lean on are asserted here and the seed is advanced until they
+    hold: they are statements about the reference's numbers alone."""
+    import scripts.compute_mmd_cov_1nn as R
+    from oracle import ref_metrics as RM
+    N, P, JSD_SCALE = 24, 256, 0.5
+    for seed in range(100, 140):
+        rng = np.random.default_rng(seed)
+        smp, ref = _shape_clouds(rng, N, P, 0.35), _shape_clouds(rng, N, P, 0.65)
+        s64, r64 = torch.from_numpy(smp).double(), torch.from_numpy(ref).double()
+        pair = lambda a, b: [t.numpy() for t in R._pairwise_EMD_CD_(a, b, 50, accelerated_cd=False, accelerated_emd=False)]
+        (cd_rs, emd_rs), (cd_rr, emd_rr), (cd_ss, emd_ss) = pair(r64, s64), pair(r64, r64), pair(s64, s64)
+        rnd = np.random.default_rng(seed + 1000)
+        sym = lambda a: (a + a.T) / 2 * (1 - np.eye(len(a)))
+        kxx, kyy, kxy = sym(rnd.uniform(0.1, 1.0, (N, N))), sym(rnd.uniform(0.1, 1.0, (N, N))), rnd.uniform(0.1, 1.0, (N, N))
+        rect = rnd.uniform(0.1, 1.0, (17, 31))
+        gaps = [_min_gap(cd_rs.T, 1), _min_gap(cd_rs.T, 0), _min_gap(_knn_joint(cd_rr, cd_rs, cd_ss), 0),
+                _min_gap(_knn_joint(kxx, kxy, kyy), 0), _min_gap(rect, 1), _min_gap(rect, 0)]
+        # nearest / second-nearest grid cell of every point (float64 brute force)
+        grid, _ = R.unit_cube_grid_point_cloud(28, True)
+        pts = np.concatenate([smp, ref]).reshape(-1, 3).astype(np.float64) * JSD_SCALE
+        cell_gap = 1.0
+        for c0 in range(0, len(pts), 1024):
+            d = ((pts[c0:c0 + 1024, None, :] - grid[None].astype(np.float64)) ** 2).sum(-1)
+            two = np.partition(d, 1, axis=1)[:, :2]
+            cell_gap = min(cell_gap, float(((two[:, 1] - two[:, 0]) / two[:, 1]).min()))
+        # the auction (numpy restatement of approxmatch.cu) against the exact assignment, pair by pair
+        ok_bracket, lo, hi = True, np.inf, 0.0
+        for a, b, exact in ((ref, smp, emd_rs), (ref, ref, emd_rr), (smp, smp, emd_ss)):
+            for i in range(N):
+                ae = np.repeat(a[i][None], N, axis=0)
+                cost = RM.matchcost(ae, b, RM.approxmatch(ae, b)) / P
+                keep = exact[i] > 0                                           # (a cloud against itself: 0 / 0)
+                ratio = cost[keep] / exact[i][keep]
+                lo, hi = min(lo, ratio.min()), max(hi, ratio.max())
+        ok_bracket = lo >= 1 - 1e-6 and hi <= 1.5
+        print(f"[shape_metrics] seed {seed}: min/runner-up gaps {min(gaps):.2e}, cell gap {cell_gap:.2e}, "
+              f"auction / exact in [{lo:.4f}, {hi:.4f}]", flush=True)
+        if min(gaps) >= 1e-3 and cell_gap >= 1e-4 and ok_bracket:
+            break
+    else:
+        raise SystemExit("no seed satisfies the fixture's conditions")
+    res = R.compute_all_metrics(s64, r64, 50, accelerated_cd=False)
+    keys = sorted(res)
+    k24 = R.knn(torch.from_numpy(kxx), torch.from_numpy(kxy), torch.from_numpy(kyy), 1, sqrt=False)
+    kkeys = sorted(k24)
+    l24, lrect = R.lgan_mmd_cov(torch.from_numpy(kxy)), R.lgan_mmd_cov(torch.from_numpy(rect))
+    lkeys = sorted(l24)
+    occ = {}
+    for tag, pcs in (("smp", smp), ("ref", ref)):
+        pc64 = pcs.astype(np.float64) * JSD_SCALE
+        ent, counters = R.entropy_of_occupancy_grid(pc64, 28, True)
+        # the per-cell cloud counts stay inside that function: rebuild them from its own counters, one cloud at a time
+        bern = sum((R.entropy_of_occupancy_grid(pc64[i:i + 1], 28, True)[1] > 0).astype(np.int64) for i in range(N))
+        occ[tag] = (ent, counters.astype(np.int64), bern)
+    jsd = R.jsd_between_point_cloud_sets(smp.astype(np.float64) * JSD_SCALE, ref.astype(np.float64) * JSD_SCALE, 28)
+    save("shape_metrics", sample=smp, ref=ref, seed=np.int64(seed), jsd_scale=np.float64(JSD_SCALE),
+         cd_rs=cd_rs, cd_rr=cd_rr, cd_ss=cd_ss, emd_rs_exact=emd_rs, emd_rr_exact=emd_rr, emd_ss_exact=emd_ss,
+         metrics_keys=np.array(keys), metrics_vals=np.array([float(res[k]) for k in keys], np.float64),
+         knn_xx=kxx, knn_xy=kxy, knn_yy=kyy, knn_keys=np.array(kkeys),
+         knn_vals=np.array([float(k24[k]) for k in kkeys], np.float64),
+         lgan_rect=rect, lgan_keys=np.array(lkeys), lgan_vals_xy=np.array([float(l24[k]) for k in lkeys], np.float64),
+         lgan_vals_rect=np.array([float(lrect[k]) for k in lkeys], np.float64),
+         counters_smp=occ["smp"][1], counters_ref=occ["ref"][1], bernoulli_smp=occ["smp"][2], bernoulli_ref=occ["ref"][2],
+         entropy_smp=np.float64(occ["smp"][0]), entropy_ref=np.float64(occ["ref"][0]), jsd=np.float64(jsd),
+         cond_min_gap=np.float64(min(gaps)), cond_cell_gap=np.float64(cell_gap), cond_auction_lo=np.float64(lo),
+         cond_auction_hi=np.float64(hi))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -677,7 +779,7 @@ def main():
     install_patches()
     todo = a.only or ["schedule", "unet_small", "unet_full", "ddim_small", "ddim_full", "vq", "gcn", "e2e",
                       "unet_concat_small", "unet_concat_full", "ddim_concat_small", "gcn_concat", "e2e_concat", "box",
-                      "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode"]
+                      "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode", "shape_metrics"]
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name in todo:
@@ -728,6 +830,8 @@ def main():
                 g_box()
             elif name == "full_manip":
                 g_full_manip(tmp)
+            elif name == "shape_metrics":
+                g_shape_metrics()
             else:
                 raise SystemExit(f"unknown fixture {name}")
 
