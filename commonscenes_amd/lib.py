@@ -180,6 +180,10 @@ SIGNATURES = {
     "cs_mc_blocks_per_object": (_i, [_i]),
     "cs_mc_count": (_i, [_f, _i, _i, _fl, _i, _f, _s]),
     "cs_mc_emit": (_i, [_f, _i, _i, _fl, _i, _f, _f, _f, _f, _f, _f, _fl, _fl, _s]),
+    "cs_scene_fit_boxes": (_i, [_f, _l, _f, _f, _f, _i, _i, _f, _f, _s]),
+    "cs_scene_apply": (_i, [_f, _l, _f, _l, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _l, _f, _f, _l, _s]),
+    "cs_scene_raster_topdown": (_i, [_f, _l, _f, _l, _i, _fl, _f, _f, _s]),
+    "cs_scene_resolve": (_i, [_f, _f, _l, _f, _l, _f, _f, _i, _f, _f, _f, _s]),
     "cs_chamfer_nm_distance": (_i, [_f, _f, _f, _f, _i, _i, _i, _s]),
     "cs_unet_create": (_i, [C.POINTER(CsUnetConfig), _pp]),
     "cs_unet_destroy": (None, [C.c_void_p]),

@@ -787,6 +787,56 @@ int cs_mc_emit(const float* sdf, int nb, int n, float level, int table, const in
                float vert_shift, cs_stream_t stream);
 
 /*
+ * Scene assembly and the top-down view (csrc/cs_scene.hip): what the reference does on the host right after sampling,
+ * helpers/visualize_scene.py:378-461 render_v2_full -> helpers/util.py:298-332 get_generated_models_v2 -> :158-189
+ * fit_shapes_to_box_v2, then :85-116 render_img (trimesh + pyrender).  Every buffer is caller-owned device memory; nothing
+ * synchronises; ranges that leave a buffer are skipped, never dereferenced.
+ *
+ * cs_scene_fit_boxes: verts [total_verts][3] fp32 is the ragged buffer cs_mc_emit writes, object i owning vert_count[i]
+ *   vertices from vert_base[i] (int64, device); box7 [n][7] fp32 = l, h, w, px, py, pz, angle (degrees if `degrees`).
+ *   Per object: the vertex bounds lo / hi, then in fp64 the map of util.py:158-189,
+ *     c = lo + (hi - lo) / 2 with c.y = lo.y;   v1 = P v - c, P (x, y, z) -> (-z, y, x) (trimesh rotation_matrix(-pi/2,
+ *     [0,1,0]) without its 6e-17 cosine);   s = max(v1) - min(v1);   v2 = v1 / s * (l, h, w);   v3 = R^T v2 + (px, py, pz)
+ *     with R = get_rotation_3dfront(angle) (:510-516).  c is taken from the UNROTATED bounds and subtracted after the
+ *     rotation, as the reference does.
+ *   -> xform [n][12] fp32: that map as a row-major 3x4 [A | t], rounded once;  box_points [n][8][3] fp32: the corners
+ *   (+-l/2, {0, h}, +-w/2) . R + t of :162-166 / :186-188, for every object.  An object without vertices gets the identity
+ *   map.  Along an axis of zero extent the reference divides by zero (inf / nan vertices); here that coordinate maps to 0
+ *   before the translation.
+ * cs_scene_apply: one pass over the objects with keep[i] != 0 (uint8), no atomics, output order = input order:
+ *   out_verts[out_vert_base[i] + v] = ((A0 x + A1 y) + A2 z) + t in fp32;  out_rgb likewise = color[i] ([n][3] fp32);
+ *   out_faces[out_face_base[i] + f] = faces[face_base[i] + f] + out_vert_base[i] (int64, scene-global ids), columns reversed
+ *   when flip != 0 (trimesh invert(), util.py:260-267);  face_object [out_nfaces] int32 = i.
+ * cs_scene_raster_topdown: render_img's camera (visualize_scene.py:85-108: eye (0, 8, 0), looking along -y, up -z,
+ *   yfov = pi/2, square image): depth = 8 - y, col = (1 + x / depth) / 2 * size, row = (1 + z / depth) / 2 * size, pixel
+ *   centres at +0.5.  Coverage is exact and order-independent: projected vertices snap to 1/256 pixel
+ *   (floor(coord * 256 + 0.5), coordinates clamped to +-2^21 pixels), integer edge functions in int64, top-left fill rule,
+ *   both windings drawn, zero-area triangles skipped, bounding boxes clamped to the image.  A triangle with a vertex at
+ *   depth < znear (pyrender's default: 0.05) or with a non-finite vertex is dropped whole -- no near-plane clipping -- and
+ *   counted in *dropped.  Depth per pixel is perspective-correct fp32, 1/d = sum_i (E_i / area) / d_i (a triangle whose three
+ *   vertices share one depth has exactly that depth, so coplanar horizontal faces tie exactly).  Visibility is one
+ *   64-bit atomic min per covered pixel on keys [size][size] uint64 = (bits of d) << 32 | face id: the nearest triangle wins,
+ *   equal depths go to the lowest face id, whatever the launch order.  The call itself resets keys and *dropped.
+ * cs_scene_resolve: keys -> depth [size][size] fp32 (+inf where empty), object_id int32 = face_object of the winning face
+ *   (-1 where empty), rgb [size][size][3] uint8 = vertex colour x (0.3 + 0.7 max(0, n_y)), n the unit normal of the face as
+ *   stored (i.e. after `flip`), so a face turned away from the camera gets the ambient term only; background 255.
+ *   The shading model is this library's: pyrender's lights (a directional and a point light at the camera) cannot be pinned
+ *   without pyrender, so colours are not comparable with the reference's images; coverage, depth and ids are.
+ */
+int cs_scene_fit_boxes(const float* verts, int64_t total_verts, const int64_t* vert_base, const int64_t* vert_count,
+                       const float* box7, int n, int degrees, float* xform, float* box_points, cs_stream_t stream);
+int cs_scene_apply(const float* verts, int64_t total_verts, const int64_t* faces, int64_t total_faces,
+                   const int64_t* vert_base, const int64_t* vert_count, const int64_t* face_base, const int64_t* face_count,
+                   const float* xform, const uint8_t* keep, const int64_t* out_vert_base, const int64_t* out_face_base,
+                   const float* color, int n, int flip, float* out_verts, float* out_rgb, int64_t out_nverts,
+                   int64_t* out_faces, int32_t* face_object, int64_t out_nfaces, cs_stream_t stream);
+int cs_scene_raster_topdown(const float* verts, int64_t nverts, const int64_t* faces, int64_t nfaces, int size, float znear,
+                            uint64_t* keys, int32_t* dropped, cs_stream_t stream);
+int cs_scene_resolve(const uint64_t* keys, const float* verts, int64_t nverts, const int64_t* faces, int64_t nfaces,
+                     const float* vert_rgb, const int32_t* face_object, int size, float* depth, int32_t* object_id,
+                     uint8_t* rgb, cs_stream_t stream);
+
+/*
  * Whole-forward driver (SURVEY 8b "cs_unet_step"): UNet3DModel.forward (openai_model_3d.py:752-789) with the
  * crossattn conditioning of DiffusionUNet.forward (network.py:28-30) as ONE call over a packed weight arena.
  * The plan object is host memory only (architecture walk, arena layout, packing recipe); every device buffer --

@@ -101,6 +101,60 @@ def build_experiment(tmp: Path, width: int):
     return opt
 
 
+def export_scene(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs):
+    """--export-scenes: the scene mesh and its top-down view, timed on the device (second call: the first loads the code
+    objects), and the host numpy restatement of fit_shapes_to_box_v2 over the same meshes for context."""
+    from commonscenes_amd import scene_mesh as S
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    classes = list(VOCAB["object_idx_to_name"])
+    classes[0], classes[-1] = "_scene_\n", "floor\n"           # synth.random_scene_graph: class 0 / the last class
+    box_and_angle = torch.cat([boxes_pred.float(), angles_pred.float()], dim=1)
+    cats = dec_objs.cpu().tolist()
+    times = {}
+    for tag in ("first_call_s", "device_s"):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        scene = S.assemble_scene(meshes, box_and_angle, cats, classes, floor=True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        img = S.render_topdown(scene, 256)
+        torch.cuda.synchronize()
+        times[tag] = time.perf_counter() - t0
+        times["assemble_s"], times["render_s"] = t1 - t0, time.perf_counter() - t1
+    t0 = time.perf_counter()                                     # the reference's host path: copy out, fit per object in fp64
+    boxes_h = box_and_angle.cpu().numpy()
+    shaped = [j for j, c in enumerate(cats) if classes[c].strip() not in ("_scene_", "floor")]
+    for j, v in zip(shaped, meshes.verts_list()):
+        v = v.cpu().numpy().astype(np.float64)
+        if v.shape[0] == 0:
+            continue
+        l, h, w, px, py, pz, ang = [float(x) for x in boxes_h[j]]
+        lo, hi = v.min(axis=0), v.max(axis=0)
+        c = lo + (hi - lo) / 2
+        c[1] = lo[1]
+        v1 = np.stack([-v[:, 2], v[:, 1], v[:, 0]], axis=1) - c[None]
+        size = v1.max(axis=0) - v1.min(axis=0)
+        y = np.deg2rad(ang)
+        rot = np.array([[np.cos(y), 0, -np.sin(y)], [0, 1, 0], [np.sin(y), 0, np.cos(y)]])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            (v1 / size * np.array([l, h, w])).dot(np.linalg.inv(rot).T) + np.array([px, py, pz])
+    times["numpy_fit_s"] = time.perf_counter() - t0
+    scene.export_obj(out / f"{scan}.obj")
+    rgb = img["rgb"].cpu().numpy()
+    try:
+        from PIL import Image
+        Image.fromarray(rgb).save(out / f"{scan}.png")
+        image = f"{scan}.png"
+    except ImportError:
+        np.save(out / f"{scan}.npy", rgb)
+        image = f"{scan}.npy"
+    nv, nf = int(scene.verts.shape[0]), int(scene.faces.shape[0])
+    # cs_scene_apply reads 12 B per vertex and 24 B per face, writes 24 B per vertex (position + colour) and 28 B per face
+    return dict(obj=f"{scan}.obj", image=image, verts=nv, faces=nf, dropped=img["dropped"],
+                covered=int((img["object_id"] >= 0).sum()), apply_bytes=36 * nv + 52 * nf, **times)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=2)
@@ -122,6 +176,11 @@ def main():
                          "scripts/eval_3dfront.py:484-513) against ONE coalesced call (VAE.sample_box_and_shape_many: each "
                          "scene's graph and shared x_T kept, one sampler + decode over all scenes' objects), same z / x_T, "
                          "and report the wall times and the per-object latent deviation")
+    ap.add_argument("--export-scenes", metavar="DIR", default=None,
+                    help="additionally assemble every scene (scene_mesh.assemble_scene with the floor: what render_v2_full "
+                         "hands to trimesh.Scene, helpers/visualize_scene.py:401-436) and render its 256x256 top-down view "
+                         "(render_img, :85-116); writes DIR/<scan>.obj and DIR/<scan>.png (.npy without PIL) and reports the "
+                         "device time next to a host numpy restatement of the fit (helpers/util.py:158-189)")
     a = ap.parse_args()
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -232,6 +291,8 @@ def main():
             torch.cuda.synchronize()
             t_scene = time.perf_counter() - t0
             nshape = shapes_pred.shape[0]
+            export = export_scene(a.export_scenes, data["scan_id"][0], meshes, boxes_pred, angles_pred, dec_objs) \
+                if a.export_scenes and rank == 0 else None
             # --evaluate_diversity
             boxes_div, angle_div, shapes_sample = [], [], []
             for _ in range(a.samples):
@@ -259,6 +320,8 @@ def main():
                                       sample_s=t_scene, verts=[int(v.shape[0]) for v in meshes.verts_list()],
                                       finite=bool(torch.isfinite(shapes_pred).all() and torch.isfinite(boxes_pred).all()),
                                       angle_range=[float(angles_pred.min()), float(angles_pred.max())]))
+            if export is not None:
+                res["scenes"][-1]["export"] = export
         torch.cuda.synchronize()
         res.update(total_s=time.perf_counter() - t_all, box_std_mean=float(np.mean(all_div_boxes)),
                    angle_std_mean=float(np.mean(all_div_angles)), chamfer_diversity_mean=float(np.mean(all_div_chamfer)),
