@@ -50,14 +50,42 @@ struct Gemm {        // one packed GEMM weight (possibly several reference tenso
   int up_mask = 0, ncls = 0, fkd = 3, fkh = 3, fkw = 3, amax_slot = -1;
   int64_t fold_off = 0, cls_w_off[8] = {0}, cls_wlo_off[8] = {0};
   float cls_acc_scale[8] = {0};
-  // r5: the Winograd-W pack of a 3x3x3 conv beside the direct one (CsConvGemm.a_format = 3, ops.py::pack_weight_wino): four
+  // the Winograd-W pack of a 3x3x3 conv beside the direct one (CsConvGemm.a_format = 3, ops.py::pack_weight_wino): four
   // position images, one power-of-two scale; -1 = the geometry can never take that route
   int64_t wino_off = -1, wino_lo_off = -1;
   float wino_acc = 1.f;
   // ... and its F(4,3) sibling (six images): CsConvGemm.a_format = 4
   int64_t wino4_off = -1, wino4_lo_off = -1;
   float wino4_acc = 1.f;
+
+  // the pack a launch reads: hi / lo image offsets and 1 / (weight scale * 16).  variant 0 = direct, 2 = F(2,3), 4 = F(4,3)
+  struct Pack {
+    int64_t w, lo;
+    float acc;
+  };
+  Pack pack(int variant) const {
+    if (variant == 4) return {wino4_off, wino4_lo_off, wino4_acc};
+    if (variant == 2) return {wino_off, wino_lo_off, wino_acc};
+    return {w_off, wlo_off, acc_scale};
+  }
+  // F16X3 images: 8-channel K groups per tap (cin rounded up to 16), bytes of one hi or lo image of ntaps taps
+  int kg() const { return (cin + 15) / 16 * 2; }
+  int64_t img_bytes(int64_t ntaps) const { return ntaps * kg() * cout * 16; }
+  // fp32 layout [tap][cin_pad][ldw]
+  int64_t f32_bytes(int64_t ntaps) const { return ntaps * cin_pad * ldw * 4; }
 };
+
+// power-of-two F16X3 weight scale of a tensor whose largest |entry| is m (2^14 / 2^ex: the scaled maximum lands in
+// [2^13, 2^14)) and the matching accumulator scale 1 / (scale * 16)
+struct WeightScale {
+  float scale, acc;
+};
+inline WeightScale weight_scale(double m) {
+  int ex = 0;
+  if (m > 0.0 && std::isfinite(m)) (void)std::frexp(m, &ex);
+  const float scale = (float)std::ldexp(1.0, 14 - ex);
+  return {scale, 1.0f / (scale * 16.0f)};
+}
 
 struct Norm {
   int gp, bp, c;
@@ -86,7 +114,7 @@ struct Plan {
   std::vector<RawCopy> copies;
   int64_t raw_bytes = 0, arena_bytes = 0, amax_off = 0;
   int amax_slots = 0;      // per-parameter |w| maxima, then one per parity class of every folded upsample conv
-  int extra_slots = 0;     // ... then this many more floats reserved by the model (cs_unet: 34 per transformer block, r5)
+  int extra_slots = 0;     // ... then this many more floats reserved by the model (cs_unet: 34 per transformer block)
   int extra_slot0 = 0;     // index of the first of them (set by layout_arena)
   bool packed = false;
 };
@@ -203,15 +231,11 @@ void layout_arena(Plan& u) {
       g.fold_off = off;
       off += align_up((int64_t)g.ncls * g.cout * g.cin * ftaps * 4);
       for (int c = 0; c < g.ncls; ++c) {
+        g.cls_w_off[c] = off;
+        off += align_up(f16 ? g.img_bytes(ftaps) : g.f32_bytes(ftaps));
         if (f16) {
-          const int64_t img = (int64_t)ftaps * ((g.cin + 15) / 16 * 2) * g.cout * 16;
-          g.cls_w_off[c] = off;
-          off += align_up(img);
           g.cls_wlo_off[c] = off;
-          off += align_up(img);
-        } else {
-          g.cls_w_off[c] = off;
-          off += align_up((int64_t)ftaps * g.cin_pad * g.ldw * 4);
+          off += align_up(g.img_bytes(ftaps));
         }
       }
       g.amax_slot = slots;
@@ -223,34 +247,29 @@ void layout_arena(Plan& u) {
       continue;
     }
     if (f16) {
-      const int64_t kg = (int64_t)(g.cin + 15) / 16 * 2;
-      const int64_t img = (int64_t)g.taps * kg * g.cout * 16;
       g.ldw = g.cout;
       g.w_off = off;
-      off += align_up(img);
+      off += align_up(g.img_bytes(g.taps));
       g.wlo_off = off;
-      off += align_up(img);
-      // (r5: the Winograd-W pack beside the direct one -- also for the input-channel halves of a channel-split conv, scaled
-      // by the whole tensor's maximum like their direct packs: ops.py::pack_weight_wino)
+      off += align_up(g.img_bytes(g.taps));
+      // the Winograd-W packs beside the direct one (four resp. six position images of nine taps) -- also for the
+      // input-channel halves of a channel-split conv, scaled by the whole tensor's maximum like their direct packs:
+      // ops.py::pack_weight_wino
       if (g.k == 3 && !g.tap_cout && g.w.size() == 1 && g.w[0].param >= 0 && g.w[0].row0 == 0 && g.w[0].rows == g.cout &&
           (g.cout % 224 == 0 || g.cout % 128 == 0 || g.cout == 64) && g.cin % 8 == 0 && g.cin >= 16 && g.cin_pad == g.cin) {
-        const int64_t wimg = 4LL * 9 * kg * g.cout * 16;
         g.wino_off = off;
-        off += align_up(wimg);
+        off += align_up(g.img_bytes(4 * 9));
         g.wino_lo_off = off;
-        off += align_up(wimg);
-        {
-          const int64_t wimg4 = 6LL * 9 * kg * g.cout * 16;
-          g.wino4_off = off;
-          off += align_up(wimg4);
-          g.wino4_lo_off = off;
-          off += align_up(wimg4);
-        }
+        off += align_up(g.img_bytes(4 * 9));
+        g.wino4_off = off;
+        off += align_up(g.img_bytes(6 * 9));
+        g.wino4_lo_off = off;
+        off += align_up(g.img_bytes(6 * 9));
       }
     } else {
       g.ldw = (g.cout + 3) / 4 * 4;
       g.w_off = off;
-      off += align_up((int64_t)g.taps * g.cin_pad * g.ldw * 4);
+      off += align_up(g.f32_bytes(g.taps));
     }
     if (!g.b.empty()) {
       g.b_off = off;
@@ -327,7 +346,7 @@ __global__ __launch_bounds__(256) void pack_part_f16x3_kernel(const float* __res
   }
 }
 
-// r5: the Winograd-W pack of a 3x3x3 conv (or of an input-channel range [c0, c0 + cin) of one): cs_pack_weight_f16x3_wino's
+// the Winograd-W pack of a 3x3x3 conv (or of an input-channel range [c0, c0 + cin) of one): cs_pack_weight_f16x3_wino's
 // arithmetic -- u_q over the kw taps formed and split in fp64 -- on a (cout, src_cin, 27) source tensor
 __global__ __launch_bounds__(256) void pack_part_f16x3_wino_kernel(const float* __restrict__ w, _Float16* __restrict__ wh,
                                                                    _Float16* __restrict__ wl, int cout, int cin,
@@ -379,10 +398,6 @@ __global__ __launch_bounds__(256) void pack_part_f32_kernel(const float* __restr
     o[((int64_t)tap * cin_pad + c) * ldw + n_off + n] = v;
   }
 }
-
-// ---------------------------------------------------------------------------------------------------------
-// execution
-// ---------------------------------------------------------------------------------------------------------
 
 // raw parameters -> arena: GEMM weights in the layout of the plan's math mode (pieces gathered into fused weights),
 // biases, norm affine parameters, verbatim copies.  One stream sync in F16X3 mode (per-tensor |w| maxima).
@@ -452,25 +467,21 @@ int pack_plan(Plan* u, const void* raw_dev, void* arena_dev, cs_stream_t stream)
     return CS_OK;
   };
   for (Gemm& g : u->gemms) {
+    const int kg = g.kg();
     if (g.up_mask) {      // one packed image (pair) per parity class, each with its own power-of-two scale
       const int ftaps = g.fkd * g.fkh * g.fkw;
       const int64_t n = (int64_t)g.cout * g.cin * ftaps;
       for (int c = 0; c < g.ncls; ++c) {
         const float* w = reinterpret_cast<const float*>(arena + g.fold_off) + c * n;
         if (f16) {
-          const float m = amax[(size_t)g.amax_slot + c];
-          int ex = 0;
-          if (m > 0.f && std::isfinite(m)) (void)std::frexp((double)m, &ex);
-          const float scale = (float)std::ldexp(1.0, 14 - ex);
-          g.cls_acc_scale[c] = 1.0f / (scale * 16.0f);
-          const int kg = (g.cin + 15) / 16 * 2;
+          const WeightScale s = weight_scale(amax[(size_t)g.amax_slot + c]);
+          g.cls_acc_scale[c] = s.acc;
           const int64_t total = (int64_t)ftaps * kg * g.cout * 8;
           CS_LAUNCH(pack_part_f16x3_kernel, dim3(cs_grid_for(total, 256, 256 * 32)), dim3(256), 0, st, w,
                     (_Float16*)(arena + g.cls_w_off[c]), (_Float16*)(arena + g.cls_wlo_off[c]), g.cout, 0, g.cout,
-                    g.cin, ftaps, kg, scale, 0, 0);
+                    g.cin, ftaps, kg, s.scale, 0, 0);
         } else {
-          if (hipMemsetAsync(arena + g.cls_w_off[c], 0, (size_t)ftaps * g.cin_pad * g.ldw * 4, st) != hipSuccess)
-            return CS_EINVAL;
+          if (hipMemsetAsync(arena + g.cls_w_off[c], 0, (size_t)g.f32_bytes(ftaps), st) != hipSuccess) return CS_EINVAL;
           const int64_t total = (int64_t)ftaps * g.cin_pad * g.cout;
           CS_LAUNCH(pack_part_f32_kernel, dim3(cs_grid_for(total, 256)), dim3(256), 0, st, w,
                     (float*)(arena + g.cls_w_off[c]), g.cout, 0, g.cin, ftaps, g.cin_pad, g.ldw, 0, 0);
@@ -483,14 +494,11 @@ int pack_plan(Plan* u, const void* raw_dev, void* arena_dev, cs_stream_t stream)
     }
     if (g.tap_cout) {     // taps as columns: the whole (tap_cout, cin, 3, 3, 3) tensor -> one pointwise image pair
       if (!f16 || g.w.size() != 1 || g.w[0].param < 0 || g.w[0].row0 != 0 || g.w[0].rows != g.tap_cout) return CS_EINVAL;
-      const float m = amax[(size_t)g.w[0].param];
-      int ex = 0;
-      if (m > 0.f && std::isfinite(m)) (void)std::frexp((double)m, &ex);
-      const float scale = (float)std::ldexp(1.0, 14 - ex);
-      g.acc_scale = 1.0f / (scale * 16.0f);
+      const WeightScale s = weight_scale(amax[(size_t)g.w[0].param]);
+      g.acc_scale = s.acc;
       int rc = cs_pack_weight_f16x3_tapcol(src(g.w[0].param), arena + g.w_off, arena + g.wlo_off, g.tap_cout, g.cin,
-                                           g.cout, scale, stream);
-      if (rc == CS_OK && !g.b.empty()) rc = copy_bias(g);
+                                           g.cout, s.scale, stream);
+      if (rc == CS_OK) rc = copy_bias(g);
       if (rc != CS_OK) return rc;
       continue;
     }
@@ -500,21 +508,19 @@ int pack_plan(Plan* u, const void* raw_dev, void* arena_dev, cs_stream_t stream)
       // scale by the whole tensor's maximum even when only a row range is used (GEGLU pieces): what
       // ops._pack_weight_f16x3 sees is the permuted full tensor, whose maximum is the same
       float m = 0.f;
-      for (const Piece& pc : g.w)
-        if (pc.param >= 0) m = fmaxf(m, amax[pc.param]);
-      int ex = 0;
-      if (m > 0.f && std::isfinite(m)) (void)std::frexp((double)m, &ex);
-      scale = (float)std::ldexp(1.0, 14 - ex);
-      g.acc_scale = 1.0f / (scale * 16.0f);
-      const int64_t img = (int64_t)g.taps * ((g.cin + 15) / 16 * 2) * g.cout * 16;
       bool zero_rows = false;
-      for (const Piece& pc : g.w) zero_rows |= pc.param < 0;
-      if (zero_rows && (hipMemsetAsync(arena + g.w_off, 0, (size_t)img, st) != hipSuccess ||
-                        hipMemsetAsync(arena + g.wlo_off, 0, (size_t)img, st) != hipSuccess))
+      for (const Piece& pc : g.w) {
+        if (pc.param >= 0) m = fmaxf(m, amax[pc.param]);
+        zero_rows |= pc.param < 0;
+      }
+      const WeightScale s = weight_scale(m);
+      scale = s.scale;
+      g.acc_scale = s.acc;
+      if (zero_rows && (hipMemsetAsync(arena + g.w_off, 0, (size_t)g.img_bytes(g.taps), st) != hipSuccess ||
+                        hipMemsetAsync(arena + g.wlo_off, 0, (size_t)g.img_bytes(g.taps), st) != hipSuccess))
         return CS_EINVAL;
     } else {
-      if (hipMemsetAsync(arena + g.w_off, 0, (size_t)g.taps * g.cin_pad * g.ldw * 4, st) != hipSuccess)
-        return CS_EINVAL;
+      if (hipMemsetAsync(arena + g.w_off, 0, (size_t)g.f32_bytes(g.taps), st) != hipSuccess) return CS_EINVAL;
     }
     int n_off = 0;
     for (const Piece& pc : g.w) {
@@ -524,7 +530,6 @@ int pack_plan(Plan* u, const void* raw_dev, void* arena_dev, cs_stream_t stream)
       }
       const float* w = src(pc.param) + (int64_t)pc.row0 * cols;
       if (f16) {
-        const int kg = (g.cin + 15) / 16 * 2;
         const int64_t total = (int64_t)g.taps * kg * pc.rows * 8;
         CS_LAUNCH(pack_part_f16x3_kernel, dim3(cs_grid_for(total, 256, 256 * 32)), dim3(256), 0, st, w,
                   (_Float16*)(arena + g.w_off), (_Float16*)(arena + g.wlo_off), pc.rows, n_off, g.cout, g.cin,
@@ -538,32 +543,18 @@ int pack_plan(Plan* u, const void* raw_dev, void* arena_dev, cs_stream_t stream)
       n_off += pc.rows;
     }
     if (n_off != g.cout) return CS_EINVAL;
-    if (f16 && g.wino_off >= 0) {      // r5: the Winograd-W pack (max |u_q| <= 1.5 max |w|: ops.py::pack_weight_wino)
-      const int kg = (g.cin + 15) / 16 * 2;
-      for (int variant = 2; variant <= (g.wino4_off >= 0 ? 4 : 2); variant += 2) {
-        // (max |u_q| <= 1.5 max |w| for F(2,3), <= max |w| for F(4,3): ops.py::pack_weight_wino)
-        const double m = (variant == 2 ? 1.5 : 1.0) * (double)amax[(size_t)g.w[0].param];
-        int ex = 0;
-        if (m > 0.0 && std::isfinite(m)) (void)std::frexp(m, &ex);
-        const float wscale = (float)std::ldexp(1.0, 14 - ex);
-        (variant == 2 ? g.wino_acc : g.wino4_acc) = 1.0f / (wscale * 16.0f);
-        CS_LAUNCH(pack_part_f16x3_wino_kernel, dim3(cs_grid_for((variant + 2LL) * 9 * kg * g.cout * 8, 256, 256 * 32)), dim3(256),
-                  0, st, src(g.w[0].param), (_Float16*)(arena + (variant == 2 ? g.wino_off : g.wino4_off)),
-                  (_Float16*)(arena + (variant == 2 ? g.wino_lo_off : g.wino4_lo_off)), g.cout, g.cin, kg, wscale, g.src_cin,
-                  g.c0, variant);
-        CS_CHECK_LAUNCH();
-      }
+    // the Winograd-W packs (max |u_q| <= 1.5 max |w| for F(2,3), <= max |w| for F(4,3): ops.py::pack_weight_wino)
+    for (int variant = 2; f16 && variant <= 4 && g.pack(variant).w >= 0; variant += 2) {
+      const WeightScale s = weight_scale((variant == 2 ? 1.5 : 1.0) * (double)amax[(size_t)g.w[0].param]);
+      (variant == 2 ? g.wino_acc : g.wino4_acc) = s.acc;
+      const Gemm::Pack pk = g.pack(variant);
+      CS_LAUNCH(pack_part_f16x3_wino_kernel, dim3(cs_grid_for((variant + 2LL) * 9 * kg * g.cout * 8, 256, 256 * 32)), dim3(256),
+                0, st, src(g.w[0].param), (_Float16*)(arena + pk.w), (_Float16*)(arena + pk.lo), g.cout, g.cin, kg, s.scale,
+                g.src_cin, g.c0, variant);
+      CS_CHECK_LAUNCH();
     }
-    n_off = 0;
-    for (const Piece& pc : g.b) {
-      if (pc.param < 0) {
-        if (hipMemsetAsync(arena + g.b_off + (int64_t)n_off * 4, 0, (size_t)pc.rows * 4, st) != hipSuccess)
-          return CS_EINVAL;
-      } else if (hipMemcpyAsync(arena + g.b_off + (int64_t)n_off * 4, src(pc.param) + pc.row0, (size_t)pc.rows * 4,
-                                hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return CS_EINVAL;
-      n_off += pc.rows;
-    }
+    const int rc = copy_bias(g);
+    if (rc != CS_OK) return rc;
   }
   for (const Norm& n : u->norms) {
     if (hipMemcpyAsync(arena + n.g_off, src(n.gp), (size_t)n.c * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
@@ -593,7 +584,7 @@ struct Buf {
   int64_t off = -1, bytes = 0;
   int64_t rows = 0;
   int c = 0;
-  // r4: the producers' partials covering this tensor's channels in order -- one segment (a GEMM output) or two (a channel
+  // the producers' partials covering this tensor's channels in order -- one segment (a GEMM output) or two (a channel
   // concatenation [h | skip]: seg[1] starts at channel seg[0].nch); released with the buffer
   Stat seg[2];
   int nseg = 0;
@@ -601,7 +592,7 @@ struct Buf {
                        // same footprint as fp32 [rows][c]
   bool pair = false;   // the INTERLEAVED operand pair (CsConvGemm.a_format = 2): bytes / row stride of fp32 [rows][c],
                        // written by cs_layernorm_pair16
-  int wino = 0;        // r5: the Winograd-W operand (CsConvGemm.a_format = 3 / 4), the variant (2 = F(2,3), 4 = F(4,3)): fp16 hi
+  int wino = 0;        // the Winograd-W operand (CsConvGemm.a_format = 3 / 4), the variant (2 = F(2,3), 4 = F(4,3)): fp16 hi
                        // images [variant + 2][voxels / variant][c] followed by the lo images -- `rows` = (variant + 2) /
                        // variant x the volume's voxels
   float a_scale = 16.f;   // F16X3 operand scale a GEMM reading this buffer uses: the default for activations of unknown
@@ -611,6 +602,43 @@ struct Buf {
 struct Act {   // an activation volume, channels-last
   Buf b;
   int nb = 0, d = 0, h = 0, w = 0;
+};
+
+// a GEMM's A operand as the kernel reads it: x (+ x_lo: the lo image of a pre-split pair / of a Winograd-W operand), row
+// stride lda, the F16X3 operand scale and CsConvGemm.a_format (0 fp32, 1 pre-split, 2 interleaved pair, 3 / 4 Winograd-W
+// F(2,3) / F(4,3)).  The sizing pass carries no pointers but the same format: the plan and tile rules look at it
+struct View {
+  const float* x = nullptr;
+  const void* x_lo = nullptr;
+  int lda = 0;
+  float a_scale = 16.f;
+  int format = 0;
+  int wino() const { return format == 4 ? 4 : format == 3 ? 2 : 0; }      // the Winograd-W variant (Gemm::pack), 0 = none
+};
+
+// what a GEMM launch sets beyond operand, weight and geometry, by name: `gemm(x, gi, nb, d, h, w,
+// GemmOpts().stats().residual(skip, skip.c))`.  The defaults are a plain stride-1 launch
+struct GemmOpts {
+  int s_hw = 1, s_d = 1;          // stride along (H, W) and along D
+  int up_hw = 0, up_d = 0;        // log2 nearest-upsample factor applied to the operand first
+  int act = CS_ACT_NONE;
+  const float* rowvec = nullptr;  // epilogue row vector: entry [row / rv_rows][ldrv] (a launch argument: NULL in the sizing
+  int ldrv = 0, rv_rows = 1;      // pass, where ldrv > 0 says that the real pass will bring one)
+  int64_t res_off = -1;           // epilogue residual [M][ldr]: the workspace offset of its buffer
+  int ldr = 0;
+  int tile = 0;                   // CsConvGemm.tile, 0 = auto
+  bool want_stats = false;        // the result feeds a GroupNorm: leave its partial sums where the launch can
+  float out_pair = 0.f;           // > 0: the only reader is the next F16X3 GEMM -- write the operand pair at this scale
+  int64_t a_bound_off = -1;       // >= 0: the operand is RAW, its magnitude bound sits in this workspace slot
+
+  GemmOpts& stride(int hw, int d) { s_hw = hw; s_d = d; return *this; }
+  GemmOpts& upsample(int hw, int d) { up_hw = hw; up_d = d; return *this; }
+  GemmOpts& activation(int a) { act = a; return *this; }
+  GemmOpts& row_vector(const float* rv, int ld, int rows) { rowvec = rv; ldrv = ld; rv_rows = rows; return *this; }
+  GemmOpts& residual(const Buf& b, int ld) { res_off = b.off; ldr = ld; return *this; }
+  GemmOpts& stats() { want_stats = true; return *this; }
+  GemmOpts& pair(float scale) { out_pair = scale; return *this; }
+  GemmOpts& bound(int64_t slot_off) { a_bound_off = slot_off; return *this; }
 };
 
 struct ExecBase {
@@ -681,12 +709,6 @@ struct ExecBase {
     sync_arena = alloc(SYNC_WORDS, 1);
     if (ok() && !dry && hipMemsetAsync(ws + sync_arena.off, 0, (size_t)SYNC_WORDS * 4, st) != hipSuccess) chk(CS_EINVAL);
   }
-  void set_sync(CsConvGemm& q) const {
-    if (q.splitk > 1 && sync_arena.off >= 0 && !dry) {
-      q.splitk_sync = reinterpret_cast<int32_t*>(ws + sync_arena.off);
-      q.splitk_sync_words = SYNC_WORDS;
-    }
-  }
   int64_t amax_slot() {       // a fresh slot's workspace offset, or -1 (feature off / arena exhausted)
     if (amax_next >= amax_cap) return -1;
     return amax_arena.off + 4 * (int64_t)amax_next++;
@@ -734,87 +756,116 @@ struct ExecBase {
     b.bytes = 0;
   }
 
-  // conv (k^3 taps, stride (1,s,s), nearest upsample (0,up,up)) or pointwise/linear GEMM with the fused epilogue
-  // want_stats: the result feeds a GroupNorm -- where the launch can (cs_conv_gemm_epilogue_caps: the one rule both hosts
-  // ask), its epilogue leaves the per-(row tile, column) partial sums and the returned buffer carries them (seg[0])
-  Buf gemm(const Buf& x, int gi, int nb, int d, int h, int w, int s_hw = 1, int up_hw = 0, int act = CS_ACT_NONE,
-           const float* rowvec = nullptr, int ldrv = 0, int rv_rows = 1, const float* res = nullptr, int ldr = 0,
-           int tile = 0, int s_d = 1, int up_d = 0, bool want_stats = false, float out_pair = 0.f,
-           int64_t a_bound_off = -1) {
-    const Gemm& g = pl.gemms[gi];
-    const bool tc = g.tap_cout > 0;      // taps as columns: the pointwise GEMM below, then cs_tapsum27
-    if (tc) {
-      if (s_hw != 1 || s_d != 1 || up_hw || up_d || act != CS_ACT_NONE || rowvec || res || tile || x.half) {
-        chk(CS_EINVAL);
-        return Buf();
-      }
-      tile = cs_tapcol_tile((int64_t)nb * d * h * w, g.cout);
-    }
-    const int k = g.k, pad = k / 2;
-    const int vh = h << up_hw, vw = w << up_hw;
-    const int dout = ((d << up_d) + 2 * pad - k) / s_d + 1;
-    const int hout = (vh + 2 * pad - k) / s_hw + 1;
-    const int wout = (vw + 2 * pad - k) / s_hw + 1;
-    const int64_t mo = (int64_t)nb * dout * hout * wout;
-    const int ocols = act == CS_ACT_GEGLU ? g.cout / 2 : g.cout;
-    Buf out = alloc(mo, ocols);
-    if (!ok()) return out;
-    if (x.c != g.cin_pad || x.rows != (x.wino ? wino_rows(x.wino, (int64_t)nb * d * h * w) : (int64_t)nb * d * h * w) ||
-        (x.wino && ((x.wino == 4 ? g.wino4_off : g.wino_off) < 0 || k != 3 || s_hw != 1 || s_d != 1 || up_hw || up_d || tile ||
-                    a_bound_off >= 0))) {
-      chk(CS_EINVAL);
-      return out;
-    }
-    CsConvGemm q;
+  // launch-argument pointer into a buffer (+ an offset in floats); the sizing pass carries none
+  float* at(const Buf& b, int64_t off = 0) const { return dry ? nullptr : p(b) + off; }
+
+  // the operand view of b from row `row0` on (a row range: fp32 and pre-split buffers only).  The lo image of a pre-split
+  // pair / of a Winograd-W operand follows the hi image's rows x c halves
+  View view(const Buf& b, int64_t row0 = 0) const {
+    View a;
+    a.lda = b.c;
+    a.a_scale = b.a_scale;
+    a.format = b.wino == 4 ? 4 : b.wino ? 3 : b.half ? 1 : b.pair ? 2 : 0;
+    if (dry) return a;
+    const bool halves = b.half || b.wino;
+    const char* base = reinterpret_cast<const char*>(p(b));
+    a.x = reinterpret_cast<const float*>(base + row0 * b.c * (halves ? 2 : 4));
+    if (halves) a.x_lo = base + (b.rows + row0) * b.c * 2;
+    return a;
+  }
+
+  // output extent of a k-tap "same"-padded conv with stride s over an extent upsampled by 2^up
+  static int conv_out(int in, int up, int k, int s) { return ((in << up) + 2 * (k / 2) - k) / s + 1; }
+
+  // THE descriptor of plan GEMM g reading operand view a of an [nb, d, h, w] volume and writing [.][ldo] rows at `out`:
+  // the weight pack that goes with the operand format, geometry, epilogue terms.  The operand format is part of what the
+  // plan and tile rules look at: it is set in the sizing pass too, so that both passes ask them about the same launch
+  void describe(CsConvGemm& q, const Gemm& g, const View& a, float* out, int ldo, int nb, int d, int h, int w,
+                const GemmOpts& o) const {
     memset(&q, 0, sizeof(q));
-    // (the operand format is part of what the tile rule looks at: set in the sizing pass too, so that both passes ask
-    // cs_conv_gemm_epilogue_caps about the same launch)
-    q.a_format = x.wino == 4 ? 4 : x.wino ? 3 : x.half ? 1 : x.pair ? 2 : 0;
+    q.a_format = a.format;
     if (!dry) {
-      q.x = p(x);
-      if (x.half) q.x_lo = reinterpret_cast<const char*>(p(x)) + x.rows * x.c * 2;
-      if (x.wino) q.x_lo = reinterpret_cast<const char*>(p(x)) + x.rows * x.c * 2;      // (the hi images' bytes)
-      q.out = p(out);
-      q.w = reinterpret_cast<const float*>(arena + (x.wino == 4 ? g.wino4_off : x.wino ? g.wino_off : g.w_off));
+      const Gemm::Pack pk = g.pack(a.wino());
+      q.x = a.x;
+      q.x_lo = a.x_lo;
+      q.out = out;
+      q.w = wf(pk.w);
       if (pl.math == CS_MATH_F16X3) {
-        q.w_lo = arena + (x.wino == 4 ? g.wino4_lo_off : x.wino ? g.wino_lo_off : g.wlo_off);
-        // g.acc_scale = 1 / (weight scale * 16); powers of two
-        q.acc_scale = (x.wino == 4 ? g.wino4_acc : x.wino ? g.wino_acc : g.acc_scale) * (16.0f / x.a_scale);
-        q.a_scale = x.a_scale;
+        q.w_lo = arena + pk.lo;
+        q.acc_scale = pk.acc * (16.0f / a.a_scale);      // pk.acc = 1 / (weight scale * 16); powers of two
+        q.a_scale = a.a_scale;
+        // a RAW activation whose magnitude bound sits in a workspace slot (range_bound / the GroupNorm over it): the kernel
+        // derives the operand scale from it instead of the fixed one (ops.py: x_bound=)
+        if (o.a_bound_off >= 0 && a.format == 0) q.a_bound = reinterpret_cast<const float*>(ws + o.a_bound_off);
       }
-      q.bias = (g.b_off >= 0 && !tc) ? wf(g.b_off) : nullptr;
-      q.rowvec = rowvec;
-      q.res = res;
+      q.bias = (g.b_off >= 0 && !g.tap_cout) ? wf(g.b_off) : nullptr;      // (taps as columns: cs_tapsum27 adds it)
+      q.rowvec = o.rowvec;
+      q.res = o.res_off >= 0 ? reinterpret_cast<const float*>(ws + o.res_off) : nullptr;
       q.status = status;
     }
     q.nb = nb; q.din = d; q.hin = h; q.win = w;
-    q.dout = dout; q.hout = hout; q.wout = wout;
+    q.dout = conv_out(d, o.up_d, g.k, o.s_d);
+    q.hout = conv_out(h, o.up_hw, g.k, o.s_hw);
+    q.wout = conv_out(w, o.up_hw, g.k, o.s_hw);
     q.cin = g.cin_pad; q.cout = g.cout;
-    q.lda = x.c; q.ldw = g.ldw; q.ldo = ocols; q.ldr = res ? ldr : 0; q.ldrv = rowvec ? ldrv : 0;
-    q.kd = q.kh = q.kw = k;
-    q.sd = s_d; q.sh = q.sw = s_hw;
-    q.pd = q.ph = q.pw = pad;
-    q.ud = up_d; q.uh = q.uw = up_hw;
-    q.act = act; q.rv_rows = rv_rows; q.math = pl.math; q.tile = tile;
-    // a_bound_off >= 0: x is a RAW activation whose magnitude bound sits in that workspace slot (range_bound / the
-    // GroupNorm over x): the kernel derives the operand scale from it instead of the fixed 16 (ops.py: x_bound=)
-    if (a_bound_off >= 0 && pl.math == CS_MATH_F16X3 && !x.half && !x.pair && !dry)
-      q.a_bound = reinterpret_cast<const float*>(ws + a_bound_off);
+    q.lda = a.lda; q.ldw = g.ldw; q.ldo = ldo; q.ldr = q.res ? o.ldr : 0; q.ldrv = q.rowvec ? o.ldrv : 0;
+    q.kd = q.kh = q.kw = g.k;
+    q.sd = o.s_d; q.sh = q.sw = o.s_hw;
+    q.pd = q.ph = q.pw = g.k / 2;
+    q.ud = o.up_d; q.uh = q.uw = o.up_hw;
+    q.act = o.act; q.rv_rows = o.rv_rows; q.math = pl.math; q.tile = o.tile;
+  }
+
+  // small batches: few output tiles -> the K loop cut into slices (cs_conv_gemm_plan, the plan function the Python host
+  // calls); Winograd-W: the position results (x K slices) live in the workspace, output transform + epilogue in the reduce
+  // kernel (cs_conv_wino_plan).  skws: the region, released by the caller after the launch.  The sizing pass allocates it too
+  bool plan_splitk(CsConvGemm& q, Buf& skws) {
+    const bool wino = q.a_format >= 3;
+    int32_t sk = 1;
+    int64_t wsb = 0;
+    if (wino) {
+      if (cs_conv_wino_plan(&q, &sk, &wsb) != CS_OK) chk(CS_EINVAL);
+    } else if (q.tile != 0 || cs_conv_gemm_plan(&q, &sk, &wsb) != CS_OK || sk <= 1) {
+      return true;
+    }
+    if (ok()) skws = alloc(wsb / 4, 1);
+    if (!ok()) return false;
+    q.splitk = sk;
+    q.splitk_ws = at(skws);
+    if (!wino && sync_arena.off >= 0 && !dry) {
+      q.splitk_sync = reinterpret_cast<int32_t*>(ws + sync_arena.off);
+      q.splitk_sync_words = SYNC_WORDS;
+    }
+    return true;
+  }
+
+  // the one GEMM path: descriptor, plan and workspace, epilogue extras, launch.  dst (optional): the Buf behind `out`, which
+  // takes the GroupNorm partials (want_stats) and the pair format (out_pair) where the launch can leave them
+  void launch_gemm(const Gemm& g, const View& a, float* out, int ldo, int nb, int d, int h, int w, const GemmOpts& o,
+                   Buf* dst = nullptr) {
+    if (a.wino() && (g.pack(a.wino()).w < 0 || g.k != 3 || pl.math != CS_MATH_F16X3 || o.s_hw != 1 || o.s_d != 1 || o.up_hw ||
+                     o.up_d || o.tile || o.a_bound_off >= 0)) {
+      chk(CS_EINVAL);
+      return;
+    }
+    CsConvGemm q;
+    describe(q, g, a, out, ldo, nb, d, h, w, o);
+    const bool extras = dst && !g.tap_cout;
     if (g.up_mask) {
       // Upsample's conv on the source grid: one GEMM per output parity class + interleave (cs_conv_gemm_up2)
-      if (g.up_mask != ((up_d << 2) | (up_hw << 1) | up_hw) || s_hw != 1 || s_d != 1 || res || rowvec || tile ||
-          x.a_scale != 16.f) {
+      if (g.up_mask != ((o.up_d << 2) | (o.up_hw << 1) | o.up_hw) || o.s_hw != 1 || o.s_d != 1 || o.res_off >= 0 || o.rowvec ||
+          o.tile || a.a_scale != 16.f) {
         chk(CS_EINVAL);
-        return out;
+        return;
       }
       const int64_t ub = cs_conv_gemm_up2_ws_bytes(&q);
       if (ub <= 0) {
         chk(CS_EINVAL);
-        return out;
+        return;
       }
       Buf uws = alloc(ub / 4, 1);
-      if (!ok()) return out;
-      if (want_stats) stats_for(q, out, nb, (int64_t)d * h * w, (int64_t)nb * d * h * w, g.ncls, g.b_off >= 0, 0, 0);
+      if (!ok()) return;
+      if (o.want_stats && extras) stats_for(q, g, o, *dst, (int64_t)d * h * w, g.ncls);
       if (!dry) {
         const void* wc[8];
         const void* wl[8];
@@ -825,148 +876,99 @@ struct ExecBase {
         chk(cs_conv_gemm_up2(&q, wc, wl, g.cls_acc_scale, p(uws), st));
       }
       release(uws);
-      return out;
+      return;
     }
-    // small batches: few output tiles -> cut the K loop into slices (same plan function the Python host calls)
-    int32_t sk = 1;
-    int64_t wsb = 0;
     Buf skws;
-    if (x.wino) {
-      // r5: the four position results (x K slices) live in the workspace; output transform + epilogue in the reduce kernel
-      if (cs_conv_wino_plan(&q, &sk, &wsb) != CS_OK) {
-        chk(CS_EINVAL);
-        return out;
-      }
-      skws = alloc(wsb / 4, 1);
-      if (!ok()) return out;
-      q.splitk = sk;
-      q.splitk_ws = dry ? nullptr : p(skws);
-    } else if (tile == 0 && cs_conv_gemm_plan(&q, &sk, &wsb) == CS_OK && sk > 1) {
-      skws = alloc(wsb / 4, 1);          // the dry run sizes the workspace with it too
-      if (!ok()) return out;
-      q.splitk = sk;
-      q.splitk_ws = dry ? nullptr : p(skws);
-      set_sync(q);
-    }
-    if (want_stats && !tc) stats_for(q, out, nb, (int64_t)dout * hout * wout, mo, 1, g.b_off >= 0, ldr, ldrv);
-    if (out_pair > 0.f && !tc && pl.math == CS_MATH_F16X3) {
+    if (!plan_splitk(q, skws)) return;
+    if (o.want_stats && extras) stats_for(q, g, o, *dst, (int64_t)q.dout * q.hout * q.wout, 1);
+    if (o.out_pair > 0.f && extras && pl.math == CS_MATH_F16X3) {
       // the result's only reader is the next F16X3 GEMM: written as the interleaved operand pair where the launch can
-      // (ops.py::conv_gemm out_pair=; the sizing pass needs no answer: same bytes either way)
-      // (asked in the sizing pass too -- same bytes either way, but the consumer's tile rule looks at its operand format)
+      // (ops.py::conv_gemm out_pair=).  Asked in the sizing pass too -- same bytes either way, but the consumer's tile rule
+      // looks at its operand format
       int32_t pair = 0;
       CsConvGemm probe = q;
-      if (dry) dry_operands(probe, g.b_off >= 0, ldr, ldrv);
+      if (dry) dry_operands(probe, g, o);
       if (!cs_debug()->no_pair_epilogue && cs_conv_gemm_epilogue_caps(&probe, nullptr, &pair) == CS_OK && pair) {
         q.out_format = 2;
-        q.out_scale = out_pair;
-        out.pair = true;
-        out.a_scale = out_pair;
+        q.out_scale = o.out_pair;
+        dst->pair = true;
+        dst->a_scale = o.out_pair;
       }
     }
     if (!dry) chk(cs_conv_gemm(&q, st));
     release(skws);      // stream-ordered: later kernels that reuse the region run after the reduce
-    if (tc) {
-      Buf o2 = alloc(mo, g.tap_cout);
+  }
+
+  // conv (k^3 taps, stride (s_d,s_hw,s_hw), nearest upsample (up_d,up_hw,up_hw)) or pointwise/linear GEMM with the fused
+  // epilogue, into a fresh buffer.  want_stats: the result feeds a GroupNorm -- where the launch can
+  // (cs_conv_gemm_epilogue_caps: the one rule both hosts ask), its epilogue leaves the per-(row tile, column) partial sums
+  // and the returned buffer carries them (seg[0])
+  Buf gemm(const Buf& x, int gi, int nb, int d, int h, int w, const GemmOpts& o = GemmOpts()) {
+    const Gemm& g = pl.gemms[gi];
+    const int64_t voxels = (int64_t)nb * d * h * w;
+    if (g.tap_cout) {      // taps as columns: the pointwise GEMM, then cs_tapsum27
+      if (o.s_hw != 1 || o.s_d != 1 || o.up_hw || o.up_d || o.act != CS_ACT_NONE || o.rowvec || o.res_off >= 0 || o.tile ||
+          x.half) {
+        chk(CS_EINVAL);
+        return Buf();
+      }
+      GemmOpts ot = o;
+      ot.tile = cs_tapcol_tile(voxels, g.cout);
+      Buf cols = gemm_fresh(x, g, nb, d, h, w, ot);
+      if (!ok()) return cols;
+      Buf out = alloc(voxels, g.tap_cout);
       if (ok() && !dry)
-        chk(cs_tapsum27(p(out), g.b_off >= 0 ? wf(g.b_off) : nullptr, p(o2), nb, d, h, w, g.tap_cout, g.cout, g.tap_cout, st));
-      release(out);
-      return o2;
+        chk(cs_tapsum27(p(cols), g.b_off >= 0 ? wf(g.b_off) : nullptr, p(out), nb, d, h, w, g.tap_cout, g.cout, g.tap_cout, st));
+      release(cols);
+      return out;
     }
+    return gemm_fresh(x, g, nb, d, h, w, o);
+  }
+  Buf gemm_fresh(const Buf& x, const Gemm& g, int nb, int d, int h, int w, const GemmOpts& o) {
+    const int64_t voxels = (int64_t)nb * d * h * w;
+    const int64_t mo =
+        (int64_t)nb * conv_out(d, o.up_d, g.k, o.s_d) * conv_out(h, o.up_hw, g.k, o.s_hw) * conv_out(w, o.up_hw, g.k, o.s_hw);
+    Buf out = alloc(mo, o.act == CS_ACT_GEGLU ? g.cout / 2 : g.cout);
+    if (!ok()) return out;
+    if (x.c != g.cin_pad || x.rows != (x.wino ? wino_rows(x.wino, voxels) : voxels)) {
+      chk(CS_EINVAL);
+      return out;
+    }
+    launch_gemm(g, view(x), at(out), out.c, nb, d, h, w, o, &out);
     return out;
   }
-  // stride-1 conv / pointwise GEMM on explicit operand views: x (+ x_lo for the pre-split pair) with row stride lda,
-  // out with row stride ldo -- channel ranges of wider buffers, sample ranges of a batch (res_block_split)
-  // wino (r5): x / x_lo are the hi / lo images of a Winograd-W operand (Buf::wino) of the [nb, d, h, w] volume
-  void gemm_view(const float* x, const void* x_lo, int lda, int gi, int nb, int d, int h, int w, float* out, int ldo,
-                 const float* rowvec = nullptr, int ldrv = 0, int rv_rows = 1, const float* res = nullptr, int ldr = 0,
-                 float a_scale = 16.f, int wino = 0) {
-    const Gemm& g = pl.gemms[gi];
-    CsConvGemm q;
-    memset(&q, 0, sizeof(q));
-    if (wino && ((wino == 4 ? g.wino4_off : g.wino_off) < 0 || g.k != 3 || pl.math != CS_MATH_F16X3)) {
-      chk(CS_EINVAL);
-      return;
-    }
-    if (wino) q.a_format = wino == 4 ? 4 : 3;
-    if (!dry) {
-      q.x = x;
-      if (x_lo) {
-        q.x_lo = x_lo;
-        if (!wino) q.a_format = 1;
-      }
-      q.out = out;
-      q.w = reinterpret_cast<const float*>(arena + (wino == 4 ? g.wino4_off : wino ? g.wino_off : g.w_off));
-      if (pl.math == CS_MATH_F16X3) {
-        q.w_lo = arena + (wino == 4 ? g.wino4_lo_off : wino ? g.wino_lo_off : g.wlo_off);
-        q.acc_scale = (wino == 4 ? g.wino4_acc : wino ? g.wino_acc : g.acc_scale) * (16.0f / a_scale);
-        q.a_scale = a_scale;
-      }
-      q.bias = g.b_off >= 0 ? wf(g.b_off) : nullptr;
-      q.rowvec = rowvec;
-      q.res = res;
-      q.status = status;
-    } else if (x_lo && !wino) {
-      q.a_format = 1;           // the plan looks at it
-    }
-    const int k = g.k, pad = k / 2;
-    q.nb = nb; q.din = d; q.hin = h; q.win = w;
-    q.dout = d; q.hout = h; q.wout = w;
-    q.cin = g.cin_pad; q.cout = g.cout;
-    q.lda = lda; q.ldw = g.ldw; q.ldo = ldo; q.ldr = res ? ldr : 0; q.ldrv = rowvec ? ldrv : 0;
-    q.kd = q.kh = q.kw = k;
-    q.sd = q.sh = q.sw = 1;
-    q.pd = q.ph = q.pw = pad;
-    q.act = CS_ACT_NONE; q.rv_rows = rv_rows; q.math = pl.math; q.tile = 0;
-    int32_t sk = 1;
-    int64_t wsb = 0;
-    Buf skws;
-    if (wino) {
-      if (cs_conv_wino_plan(&q, &sk, &wsb) != CS_OK) {
-        chk(CS_EINVAL);
-        return;
-      }
-      skws = alloc(wsb / 4, 1);
-      if (!ok()) return;
-      q.splitk = sk;
-      q.splitk_ws = dry ? nullptr : p(skws);
-    } else if (cs_conv_gemm_plan(&q, &sk, &wsb) == CS_OK && sk > 1) {
-      skws = alloc(wsb / 4, 1);
-      if (!ok()) return;
-      q.splitk = sk;
-      q.splitk_ws = dry ? nullptr : p(skws);
-      set_sync(q);
-    }
-    if (!dry) chk(cs_conv_gemm(&q, st));
-    release(skws);
+  Buf linear(const Buf& x, int gi, const GemmOpts& o = GemmOpts()) { return gemm(x, gi, (int)x.rows, 1, 1, 1, o); }
+  // the same path on explicit views -- channel ranges of wider buffers, sample ranges of a batch (res_block_split): a
+  // stride-1 conv / pointwise GEMM of operand view a into rows of stride ldo at `out`
+  void gemm_view(const View& a, int gi, int nb, int d, int h, int w, float* out, int ldo, const GemmOpts& o = GemmOpts()) {
+    launch_gemm(pl.gemms[gi], a, out, ldo, nb, d, h, w, o);
   }
 
   // ops.py::_epilogue_extras: ask the library what the launch's epilogue can emit and point the descriptor at a fresh
-  // partials region (rps = rows per sample the statistics tiles run over, m_rows = the rows they cover in all)
-  // the sizing pass carries no pointers, but cs_conv_gemm_epilogue_caps looks at which epilogue terms exist (and at their
+  // partials region (rps = rows per sample -- per class -- the statistics tiles run over).
+  // The sizing pass carries no pointers, but cs_conv_gemm_epilogue_caps looks at which epilogue terms exist (and at their
   // alignment): aligned stand-ins for exactly the operands the real pass will set, so both passes get the same answer
-  static void dry_operands(CsConvGemm& probe, bool bias, int ldr, int ldrv) {
+  static void dry_operands(CsConvGemm& probe, const Gemm& g, const GemmOpts& o) {
     const float* some = reinterpret_cast<const float*>((uintptr_t)256);
     probe.out = const_cast<float*>(some);
-    probe.bias = bias ? some : nullptr;
-    probe.res = ldr > 0 ? some : nullptr;
-    probe.ldr = ldr;
-    probe.rowvec = ldrv > 0 ? some : nullptr;
-    probe.ldrv = ldrv;
+    probe.bias = g.b_off >= 0 ? some : nullptr;
+    probe.res = o.ldr > 0 ? some : nullptr;
+    probe.ldr = o.ldr;
+    probe.rowvec = o.ldrv > 0 ? some : nullptr;
+    probe.ldrv = o.ldrv;
   }
-  void stats_for(CsConvGemm& q, Buf& out, int nb, int64_t rps, int64_t m_rows, int ncls, bool dry_bias, int dry_ldr,
-                 int dry_ldrv) {
+  void stats_for(CsConvGemm& q, const Gemm& g, const GemmOpts& o, Buf& out, int64_t rps, int ncls) {
     if (cs_debug()->no_gn_parts || pl.math != CS_MATH_F16X3) return;
     CsConvGemm probe = q;
-    if (dry) dry_operands(probe, dry_bias, dry_ldr, dry_ldrv);
+    if (dry) dry_operands(probe, g, o);
     int32_t rows = 0;
     if (cs_conv_gemm_epilogue_caps(&probe, &rows, nullptr) != CS_OK || rows <= 0) return;
     if (stats_invariant_only) {
-      // r5: only where ONE sample's launch picks the same statistics tiles (ops.py::_epilogue_extras, stats="invariant"):
-      // the VQ decoder's bit-exact batch invariance
-      // (the SAME kernel variant -- tile code, slab width, statistics rows -- at one sample, at the decode slice limit of
-      // sixteen and at this batch: ops.py::_epilogue_extras)
+      // only where ONE sample's launch picks the same statistics tiles (ops.py::_epilogue_extras, stats="invariant": the VQ
+      // decoder's bit-exact batch invariance) -- the SAME kernel variant (tile code, slab width, statistics rows) at one
+      // sample, at the decode slice limit of sixteen and at this batch
       int32_t t0 = 0, s0 = 0;
-      if (nb > 16 || cs_conv_gemm_launch_info(&probe, &t0, &s0) != CS_OK) return;
+      if (q.nb > 16 || cs_conv_gemm_launch_info(&probe, &t0, &s0) != CS_OK) return;
       for (int nbp : {1, 16}) {
         CsConvGemm one = probe;
         one.nb = nbp;
@@ -976,8 +978,8 @@ struct ExecBase {
           return;
       }
     }
-    const int64_t tiles = (m_rows + rows - 1) / rows;
-    Stat sx = alloc_stat((int64_t)ncls * tiles, q.cout, nb, (int)(rps / rows), ncls);
+    const int64_t tiles = (q.nb * rps + rows - 1) / rows;
+    Stat sx = alloc_stat((int64_t)ncls * tiles, q.cout, q.nb, (int)(rps / rows), ncls);
     if (!ok()) return;
     out.seg[0] = sx;
     out.nseg = 1;
@@ -995,7 +997,15 @@ struct ExecBase {
     }
     return n == x.c;
   }
-  // (mean, rstd) from the producers' partials: ops.py::groupnorm_stats_from_parts
+  float* bound_ptr(int64_t off) const { return off >= 0 ? reinterpret_cast<float*>(ws + off) : nullptr; }
+  // (mean, rstd) -> stats (may be NULL) and the magnitude bound -> slot boff (may be -1) from the producers' partials:
+  // ops.py::groupnorm_stats_from_parts
+  void finalize_parts(const Buf& x, int nb, float eps, int groups, float* stats, int64_t boff) {
+    if (!ok() || dry) return;
+    CsGnSeg sg[2];
+    seg_array(x, sg);
+    chk(cs_groupnorm_finalize_parts(sg, x.nseg, nb, (int)(x.rows / nb), x.c, groups, eps, stats, bound_ptr(boff), st));
+  }
   void seg_array(const Buf& x, CsGnSeg* sg) const {
     int ch0 = 0;
     for (int i = 0; i < x.nseg; ++i) {
@@ -1006,13 +1016,36 @@ struct ExecBase {
       ch0 += a.nch;
     }
   }
-  float* bound_ptr(int64_t off) const { return off >= 0 ? reinterpret_cast<float*>(ws + off) : nullptr; }
-  void finalize_parts(const Buf& x, int nb, float eps, int groups, const Buf& stats, int64_t bound_off = -1) {
-    if (!ok() || dry) return;
-    CsGnSeg sg[2];
-    seg_array(x, sg);
-    chk(cs_groupnorm_finalize_parts(sg, x.nseg, nb, (int)(x.rows / nb), x.c, groups, eps, p(stats), bound_ptr(bound_off), st));
+  // GroupNorm, step one: the statistics of x and (want_bound: a consumer will read x RAW, ops.py::groupnorm bound=) its
+  // magnitude bound in a fresh slot (-1: feature off / arena exhausted).  The source is the producers' partials -- the
+  // tensor is then read once -- or a statistics pass, which needs scratch.  alloc / run / release are separate because the
+  // single-launch forms of groupnorm() compute the statistics themselves
+  struct GnStats {
+    Buf stats, wsb;
+    int64_t bound = -1;
+    bool parts = false;
+  };
+  GnStats gn_stats_alloc(const Buf& x, int nb, int groups, bool want_bound) {
+    GnStats s;
+    s.parts = has_parts(x);
+    if (!s.parts) s.wsb = alloc((cs_groupnorm_ws_bytes(nb, groups) + 3) / 4, 1);
+    s.stats = alloc((int64_t)nb * groups * 2, 1);
+    if (want_bound) s.bound = amax_slot();
+    return s;
   }
+  void gn_stats_run(const Buf& x, int nb, float eps, int groups, const GnStats& s) {
+    if (s.parts) return finalize_parts(x, nb, eps, groups, at(s.stats), s.bound);
+    if (!ok() || dry) return;
+    const int rows = (int)(x.rows / nb);
+    chk(s.bound >= 0
+            ? cs_groupnorm_stats_bound(p(x), nb, rows, x.c, x.c, groups, eps, p(s.wsb), p(s.stats), bound_ptr(s.bound), st)
+            : cs_groupnorm_stats(p(x), nb, rows, x.c, x.c, groups, eps, p(s.wsb), p(s.stats), st));
+  }
+  void gn_stats_release(GnStats& s) {
+    release(s.wsb);
+    release(s.stats);
+  }
+
   // ops.py::range_bound: the magnitude bound of a RAW tensor that no GroupNorm follows, from its producers' partials, into
   // a fresh slot; -1 when x carries none (the consumer then keeps the fixed scale)
   int64_t range_bound(const Buf& x, int nb, int groups = 32) {
@@ -1020,89 +1053,94 @@ struct ExecBase {
     const int64_t off = amax_slot();
     if (off < 0) return -1;
     if (has_parts(x)) {
-      if (ok() && !dry) {
-        CsGnSeg sg[2];
-        seg_array(x, sg);
-        chk(cs_groupnorm_finalize_parts(sg, x.nseg, nb, (int)(x.rows / nb), x.c, groups, 1e-5f, nullptr, bound_ptr(off), st));
-      }
+      finalize_parts(x, nb, 1e-5f, groups, nullptr, off);
       return off;
     }
     // no partials (e.g. a folded Upsample conv at a small batch): one statistics pass over the (small) tensor
-    Buf wsb = alloc((cs_groupnorm_ws_bytes(nb, groups) + 3) / 4, 1);
-    Buf stats = alloc((int64_t)nb * groups * 2, 1);
-    if (ok() && !dry)
-      chk(cs_groupnorm_stats_bound(p(x), nb, (int)(x.rows / nb), x.c, x.c, groups, 1e-5f, p(wsb), p(stats), bound_ptr(off), st));
-    release(wsb);
-    release(stats);
+    GnStats s;
+    s.wsb = alloc((cs_groupnorm_ws_bytes(nb, groups) + 3) / 4, 1);
+    s.stats = alloc((int64_t)nb * groups * 2, 1);
+    s.bound = off;
+    gn_stats_run(x, nb, 1e-5f, groups, s);
+    gn_stats_release(s);
     return off;
   }
-  // the statistics pass of a tensor without partials; leaves the magnitude bound too when a slot is given
-  void stats_pass(const Buf& x, int nb, float eps, int groups, const Buf& wsb, const Buf& stats, int64_t boff) {
-    if (!ok() || dry) return;
-    const int rows = (int)(x.rows / nb);
-    chk(boff >= 0 ? cs_groupnorm_stats_bound(p(x), nb, rows, x.c, x.c, groups, eps, p(wsb), p(stats), bound_ptr(boff), st)
-                  : cs_groupnorm_stats(p(x), nb, rows, x.c, x.c, groups, eps, p(wsb), p(stats), st));
-  }
 
-  // bound_off (out): the slot x's magnitude bound went to (-1: none -- x carries no partials or the feature is off)
-  Buf gn_stats(const Buf& x, int nb, float eps, int groups = 32, int64_t* bound_off = nullptr) {
-    if (bound_off) *bound_off = -1;
-    if (has_parts(x)) {
-      Buf stats = alloc((int64_t)nb * groups * 2, 1);
-      const int64_t off = bound_off ? amax_slot() : -1;
-      finalize_parts(x, nb, eps, groups, stats, off);
-      if (bound_off) *bound_off = off;
-      return stats;
+  // GroupNorm, step two: the buffer for c normalised channels of rows_total rows in the operand format the consuming conv
+  // `conv_gi` (-1: none) wants -- wn > 0: the Winograd-W operand, variant wn (what wants_wino answered), at 1/2 resp. 1/16 of
+  // the normalisation's operand scale (|transformed| <= 2 x resp. 10 x the activation's bound; ops.py::groupnorm wino=);
+  // else the pre-split pair where wants_split16 says so for m_launch rows per launch of that conv; else fp32 -- ...
+  Buf gn_out(const Norm& n, int64_t rows_total, int c, int nb, int cpg, int wn, int conv_gi, int64_t m_launch) {
+    Buf y = alloc(wn ? wino_rows(wn, rows_total) : rows_total, c);
+    if (pl.math == CS_MATH_F16X3) y.a_scale = norm_a_scale(n.gmax, n.bmax, rows_total / nb * cpg);
+    if (wn) {
+      y.wino = wn;
+      y.a_scale *= wn == 2 ? 0.5f : 0.0625f;
+    } else {
+      y.half = wants_split16(m_launch, conv_gi);
     }
-    Buf wsb = alloc((cs_groupnorm_ws_bytes(nb, groups) + 3) / 4, 1);
-    Buf stats = alloc((int64_t)nb * groups * 2, 1);
-    const int64_t off = bound_off ? amax_slot() : -1;
-    if (bound_off) *bound_off = off;
-    stats_pass(x, nb, eps, groups, wsb, stats, off);
-    release(wsb);
-    return stats;
-  }
-  // GroupNorm apply of channels [ch0, ch0 + c) (x already points at channel ch0, row stride ldx) -> a fresh [rows][c]
-  // buffer, fp32 or the pre-split pair depending on the consuming conv
-  // variant > 0 (r5): emit the Winograd-W operand of the [nb, vd, vh, vw] volume instead (what wants_wino answered);
-  // stats_off: first sample's offset (in samples) into `stats`
-  Buf gn_apply_range(const float* x, int ldx, int64_t rows_total, int nb, const Buf& stats, int ni, int groups, int cpg,
-                     int ch0, int c, int act, int conv_gi, int64_t m_launch, int variant = 0, int vd = 0, int vh = 0, int vw = 0,
-                     int64_t stats_off = 0) {
-    const Norm& n = pl.norms[ni];
-    Buf y = alloc(variant ? wino_rows(variant, rows_total) : rows_total, c);
-    const int rows = (int)(rows_total / nb);
-    if (pl.math == CS_MATH_F16X3) y.a_scale = norm_a_scale(n.gmax, n.bmax, (int64_t)rows * cpg);
-    if (variant) {
-      y.wino = variant;
-      y.a_scale *= variant == 2 ? 0.5f : 0.0625f;
-      if (ok() && !dry) {
-        char* vhi = reinterpret_cast<char*>(p(y));
-        chk(cs_groupnorm_apply_wino_range(x, p(stats) + stats_off * groups * 2, wf(n.g_off) + ch0, wf(n.b_off) + ch0, vhi,
-                                          vhi + y.rows * c * 2, nb, vd, vh, vw, c, ldx, c, groups, cpg, ch0, act, y.a_scale,
-                                          variant, status, st));
-      }
-      return y;
-    }
-    if (wants_split16(m_launch, conv_gi)) {      // m_launch: rows per launch of the consuming conv
-      y.half = true;
-      if (ok() && !dry) {
-        char* yh = reinterpret_cast<char*>(p(y));
-        chk(cs_groupnorm_apply_split16_range(x, p(stats), wf(n.g_off) + ch0, wf(n.b_off) + ch0, yh,
-                                             yh + rows_total * c * 2, nb, rows, c, ldx, c, groups, cpg, ch0, act,
-                                             y.a_scale, status, st));
-      }
-      return y;
-    }
-    if (ok() && !dry)
-      chk(cs_groupnorm_apply_range(x, p(stats), wf(n.g_off) + ch0, wf(n.b_off) + ch0, p(y), nb, rows, c, ldx, c, groups,
-                                   cpg, ch0, act, st));
     return y;
   }
+  // ... and the apply (+ activation) that fills it with channels [ch0, ch0 + y.c) of the normalised tensor: x points at
+  // channel ch0 of the first row, row stride ldx; nb samples of `rows` rows (the Winograd-W operand: of the d x h x w
+  // volume); stats = their (mean, rstd) pairs
+  void gn_emit(const float* x, int ldx, const float* stats, const Norm& n, const Buf& y, int nb, int rows, int d, int h, int w,
+               int groups, int cpg, int ch0, int act) {
+    if (!ok() || dry) return;
+    const float *gamma = wf(n.g_off) + ch0, *beta = wf(n.b_off) + ch0;
+    const int c = y.c;
+    char* hi = reinterpret_cast<char*>(p(y));
+    if (y.wino)
+      chk(cs_groupnorm_apply_wino_range(x, stats, gamma, beta, hi, hi + y.rows * c * 2, nb, d, h, w, c, ldx, c, groups, cpg, ch0,
+                                        act, y.a_scale, y.wino, status, st));
+    else if (y.half)
+      chk(cs_groupnorm_apply_split16_range(x, stats, gamma, beta, hi, hi + y.rows * c * 2, nb, rows, c, ldx, c, groups, cpg, ch0,
+                                           act, y.a_scale, status, st));
+    else
+      chk(cs_groupnorm_apply_range(x, stats, gamma, beta, p(y), nb, rows, c, ldx, c, groups, cpg, ch0, act, st));
+  }
 
-  Buf linear(const Buf& x, int gi, int act = CS_ACT_NONE, const float* rowvec = nullptr, int ldrv = 0,
-             int rv_rows = 1, const float* res = nullptr, int ldr = 0, int tile = 0, float out_pair = 0.f) {
-    return gemm(x, gi, (int)x.rows, 1, 1, 1, 1, 0, act, rowvec, ldrv, rv_rows, res, ldr, tile, 1, 0, false, out_pair);
+  // GroupNorm (+ activation) of x, nb samples.  conv_gi: the 3x3x3 conv that consumes the result (decides the output
+  // format), or -1; d, h, w: the volume's extents where that conv may take the Winograd-W route (the ResBlocks), else 0;
+  // bound_off (out, optional): wanted when a consumer will read x RAW (the ResBlock's skip conv) -- the slot x's magnitude
+  // bound went to, -1 if none.  ops.py::groupnorm
+  Buf groupnorm(const Buf& x, int ni, int nb, float eps, int act, int groups = 32, int conv_gi = -1,
+                int64_t* bound_off = nullptr, int d = 0, int h = 0, int w = 0) {
+    const Norm& n = pl.norms[ni];
+    const int rows = (int)(x.rows / nb), cpg = x.c / groups;
+    Buf y = gn_out(n, x.rows, x.c, nb, cpg, wants_wino(conv_gi, nb, d, h, w), conv_gi, x.rows);
+    GnStats s = gn_stats_alloc(x, nb, groups, bound_off != nullptr);
+    if (bound_off) *bound_off = s.bound;
+    if (y.wino || y.half || (!s.parts && s.bound >= 0)) {
+      gn_stats_run(x, nb, eps, groups, s);
+      gn_emit(at(x), x.c, at(s.stats), n, y, nb, rows, d, h, w, groups, cpg, 0, act);
+    } else if (ok() && !dry) {
+      // fp32 result: ONE call each -- from partials a single launch for small tensors, finalize + apply otherwise
+      // (cs_groupnorm_parts decides); without partials and without a bound cs_groupnorm (one launch while the tensor is small)
+      if (s.parts) {
+        CsGnSeg sg[2];
+        seg_array(x, sg);
+        chk(cs_groupnorm_parts(p(x), sg, x.nseg, wf(n.g_off), wf(n.b_off), p(y), nb, rows, x.c, x.c, x.c, groups, eps, act,
+                               p(s.stats), bound_ptr(s.bound), st));
+      } else {
+        chk(cs_groupnorm(p(x), wf(n.g_off), wf(n.b_off), p(y), nb, rows, x.c, x.c, x.c, groups, eps, act, p(s.wsb), p(s.stats),
+                         st));
+      }
+    }
+    gn_stats_release(s);
+    return y;
+  }
+  Buf layernorm(const Buf& x, int ni) {
+    const Norm& n = pl.norms[ni];
+    Buf y = alloc(x.rows, x.c);
+    if (pl.math == CS_MATH_F16X3) y.a_scale = norm_a_scale(n.gmax, n.bmax, x.c);
+    // LayerNorm outputs only ever feed GEMMs: in F16X3 mode they are written as the interleaved operand pair
+    // (ops.py::layernorm pair_scale; CS_NO_PAIR16=1 keeps fp32 for A/B runs)
+    y.pair = pl.math == CS_MATH_F16X3 && !cs_debug()->no_pair16 && x.c % 16 == 0;
+    if (!ok() || dry) return y;
+    chk(y.pair ? cs_layernorm_pair16(p(x), wf(n.g_off), wf(n.b_off), p(y), (int)x.rows, x.c, x.c, x.c, 1e-5f, y.a_scale, status, st)
+               : cs_layernorm(p(x), wf(n.g_off), wf(n.b_off), p(y), (int)x.rows, x.c, x.c, x.c, 1e-5f, st));
+    return y;
   }
 
   // does the GroupNorm feeding conv `gi` over m output rows emit the pre-split operand pair?  (cs_conv_wants_split16: the
@@ -1112,50 +1150,8 @@ struct ExecBase {
     const Gemm& g = pl.gemms[gi];
     return cs_conv_wants_split16(m, g.cin, g.cout, g.k, !g.up_mask && !g.tap_cout && g.cin_pad == g.cin, pl.math) != 0;
   }
-
-  // r6: the F16X3 operand scales of an attention block fed by a GroupNorm (cs_attnblock_static_scales: the one rule; vqvae.py /
-  // unet.py call it with the same statistics) -- false: feature off / not F16X3 / no statistics, the constant 16 then
-  bool attnblock_scales(int norm, int64_t n_per_group, int c, float w_l2max, float b_absmax, float qk_scale, float out4[4]) const {
-    if (pl.math != CS_MATH_F16X3 || cs_debug()->no_static_scales || !(w_l2max > 0.f)) return false;
-    const Norm& nm = pl.norms[norm];
-    return cs_attnblock_static_scales(nm.gmax, nm.bmax, n_per_group, c, w_l2max, b_absmax, qk_scale, out4) == CS_OK;
-  }
-
-  // self-attention over a fused [rows][3c] q | k | v buffer -> a [rows][c]; F16X3: K / V tile images in a scratch buffer
-  // where the library has that path (cs_attn_f16x3_ws_bytes > 0)
-  // qkv_scales (r5): the static-bound operand scales of q * scale, k, v (cs_transformer_static_scales), or nullptr = 16
-  void self_attention(const Buf& qkv, const Buf& a, int nb, int n, int heads, int dh, int c, float scale,
-                      const float* qkv_scales = nullptr) {
-    Buf ws;
-    if (qkv_scales && pl.math == CS_MATH_F16X3) {
-      // (r6: the image path too -- cs_attn_selfattn_f16x3_ws_scaled; ops.py::attention does the same)
-      const int64_t wsb2 = cs_attn_f16x3_ws_bytes(nb, n, n, heads, dh);
-      if (wsb2 > 0) ws = alloc(wsb2 / 4, 1);
-      if (ok() && !dry) {
-        const float* q = p(qkv);
-        chk(wsb2 > 0 ? cs_attn_selfattn_f16x3_ws_scaled(q, q + c, q + 2 * c, p(a), nb, n, n, heads, dh, 3 * c, 3 * c, 3 * c, c,
-                                                        scale, qkv_scales[0], qkv_scales[1], qkv_scales[2], status, (void*)p(ws), st)
-                     : cs_attn_selfattn_f16x3_scaled(q, q + c, q + 2 * c, p(a), nb, n, n, heads, dh, 3 * c, 3 * c, 3 * c, c, scale,
-                                                     qkv_scales[0], qkv_scales[1], qkv_scales[2], status, st));
-      }
-      if (wsb2 > 0) release(ws);
-      return;
-    }
-    const int64_t wsb = pl.math == CS_MATH_F16X3 ? cs_attn_f16x3_ws_bytes(nb, n, n, heads, dh) : 0;
-    if (wsb > 0) ws = alloc(wsb / 4, 1);
-    if (ok() && !dry) {
-      const float* q = p(qkv);
-      chk(pl.math == CS_MATH_F16X3
-              ? cs_attn_selfattn_f16x3_ws(q, q + c, q + 2 * c, p(a), nb, n, n, heads, dh, 3 * c, 3 * c, 3 * c, c, scale,
-                                          status, wsb > 0 ? (void*)p(ws) : nullptr, st)
-              : cs_attn_selfattn(q, q + c, q + 2 * c, p(a), nb, n, n, heads, dh, 3 * c, 3 * c, 3 * c, c, scale, st));
-    }
-    if (wsb > 0) release(ws);
-  }
-
-  // r5: does the GroupNorm feeding the 3x3x3 conv `gi` over an [nb, d, h, w] volume emit the Winograd-W operand?
-  // (cs_conv_wino_ok: the one rule; ops.py::wants_wino)
-  // (the variant: 0 = direct form, 2 = F(2,3), 4 = F(4,3))
+  // does the GroupNorm feeding the 3x3x3 conv `gi` over an [nb, d, h, w] volume emit the Winograd-W operand, and which
+  // variant (0 = direct form, 2 = F(2,3), 4 = F(4,3))?  (cs_conv_wino_ok: the one rule; ops.py::wants_wino)
   int wants_wino(int gi, int nb, int d, int h, int w) const {
     if (gi < 0 || d <= 0 || pl.math != CS_MATH_F16X3 || cs_debug()->no_split16) return 0;
     const Gemm& g = pl.gemms[gi];
@@ -1172,109 +1168,36 @@ struct ExecBase {
   }
   // rows of the Buf that holds variant v's operand of a volume of `voxels` rows
   static int64_t wino_rows(int v, int64_t voxels) { return voxels / v * (v + 2); }
-  // GroupNorm + activation emitted as the Winograd-W operand (y: 2 * x.rows "rows", see Buf::wino) at HALF the
-  // normalisation's operand scale (ops.py::groupnorm wino=True)
-  void emit_wino(const Buf& x, const Norm& n, const Buf& stats, Buf& y, int nb, int d, int h, int w, int groups, int act,
-                 int variant) {
-    y.wino = variant;
-    y.a_scale *= variant == 2 ? 0.5f : 0.0625f;      // |transformed| <= 2 x resp. 10 x the activation's bound
-    if (ok() && !dry) {
-      char* vh = reinterpret_cast<char*>(p(y));
-      chk(cs_groupnorm_apply_wino_range(p(x), p(stats), wf(n.g_off), wf(n.b_off), vh, vh + y.rows * x.c * 2, nb, d, h, w, x.c,
-                                        x.c, x.c, groups, x.c / groups, 0, act, y.a_scale, variant, status, st));
-    }
+
+  // the F16X3 operand scales of an attention block fed by a GroupNorm (cs_attnblock_static_scales: the one rule; vqvae.py /
+  // unet.py call it with the same statistics) -- false: feature off / not F16X3 / no statistics, the constant 16 then
+  bool attnblock_scales(int norm, int64_t n_per_group, int c, float w_l2max, float b_absmax, float qk_scale, float out4[4]) const {
+    if (pl.math != CS_MATH_F16X3 || cs_debug()->no_static_scales || !(w_l2max > 0.f)) return false;
+    const Norm& nm = pl.norms[norm];
+    return cs_attnblock_static_scales(nm.gmax, nm.bmax, n_per_group, c, w_l2max, b_absmax, qk_scale, out4) == CS_OK;
   }
 
-  // conv_gi: the 3x3x3 conv that consumes the result (decides the output format), or -1
-  // bound_off (out, optional): wanted when a consumer will read x RAW (the ResBlock's skip conv): the slot x's magnitude
-  // bound went to, -1 if none (ops.py::groupnorm bound=)
-  // vd, vh, vw (r5): the volume's extents where the consumer may take the Winograd-W route (the UNet's ResBlocks)
-  Buf groupnorm(const Buf& x, int ni, int nb, float eps, int act, int groups = 32, int conv_gi = -1,
-                int64_t* bound_off = nullptr, int vd = 0, int vh = 0, int vw = 0) {
-    const Norm& n = pl.norms[ni];
-    const int wn = wants_wino(conv_gi, nb, vd, vh, vw);
-    Buf y = alloc(wn ? wino_rows(wn, x.rows) : x.rows, x.c);
-    if (bound_off) *bound_off = -1;
-    if (has_parts(x)) {      // r4: statistics from the producers' partials, the tensor is read once (ops.py::groupnorm)
-      const int64_t boff = bound_off ? amax_slot() : -1;
-      if (bound_off) *bound_off = boff;
-      Buf stats = alloc((int64_t)nb * groups * 2, 1);
-      if (pl.math == CS_MATH_F16X3) y.a_scale = norm_a_scale(n.gmax, n.bmax, (x.rows / nb) * (int64_t)(x.c / groups));
-      const int rows = (int)(x.rows / nb);
-      if (wn) {
-        finalize_parts(x, nb, eps, groups, stats, boff);
-        emit_wino(x, n, stats, y, nb, vd, vh, vw, groups, act, wn);
-      } else if (wants_split16(x.rows, conv_gi)) {
-        y.half = true;
-        finalize_parts(x, nb, eps, groups, stats, boff);
-        if (ok() && !dry) {
-          char* yh = reinterpret_cast<char*>(p(y));
-          chk(cs_groupnorm_apply_split16(p(x), p(stats), wf(n.g_off), wf(n.b_off), yh, yh + x.rows * x.c * 2, nb, rows, x.c,
-                                         x.c, x.c, groups, act, y.a_scale, status, st));
-        }
-      } else if (ok() && !dry) {
-        // one call: a single launch for small tensors, finalize + apply otherwise (cs_groupnorm_parts decides)
-        CsGnSeg sg[2];
-        seg_array(x, sg);
-        chk(cs_groupnorm_parts(p(x), sg, x.nseg, wf(n.g_off), wf(n.b_off), p(y), nb, rows, x.c, x.c, x.c, groups, eps, act,
-                               p(stats), bound_ptr(boff), st));
-      }
-      release(stats);
-      return y;
+  // self-attention over a fused [rows][3c] q | k | v buffer -> a [rows][c]; F16X3: K / V tile images in a scratch buffer
+  // where the library has that path (cs_attn_f16x3_ws_bytes > 0; ops.py::attention does the same)
+  // qkv_scales: the static-bound operand scales of q * scale, k, v (cs_transformer_static_scales), or nullptr = 16
+  void self_attention(const Buf& qkv, const Buf& a, int nb, int n, int heads, int dh, int c, float scale,
+                      const float* qkv_scales = nullptr) {
+    const bool f16 = pl.math == CS_MATH_F16X3;
+    const int64_t wsb = f16 ? cs_attn_f16x3_ws_bytes(nb, n, n, heads, dh) : 0;
+    Buf img;
+    if (wsb > 0) img = alloc(wsb / 4, 1);
+    if (ok() && !dry) {
+      const float *q = p(qkv), *k = q + c, *v = q + 2 * c, *s = qkv_scales;
+      const int ld = 3 * c;
+      void* iw = wsb > 0 ? (void*)p(img) : nullptr;
+      chk(!f16 ? cs_attn_selfattn(q, k, v, p(a), nb, n, n, heads, dh, ld, ld, ld, c, scale, st)
+          : !s ? cs_attn_selfattn_f16x3_ws(q, k, v, p(a), nb, n, n, heads, dh, ld, ld, ld, c, scale, status, iw, st)
+          : iw ? cs_attn_selfattn_f16x3_ws_scaled(q, k, v, p(a), nb, n, n, heads, dh, ld, ld, ld, c, scale, s[0], s[1], s[2],
+                                                  status, iw, st)
+               : cs_attn_selfattn_f16x3_scaled(q, k, v, p(a), nb, n, n, heads, dh, ld, ld, ld, c, scale, s[0], s[1], s[2], status,
+                                               st));
     }
-    Buf wsb = alloc((cs_groupnorm_ws_bytes(nb, groups) + 3) / 4, 1);
-    Buf stats = alloc((int64_t)nb * groups * 2, 1);
-    const int64_t boff = bound_off ? amax_slot() : -1;
-    if (bound_off) *bound_off = boff;
-    if (pl.math == CS_MATH_F16X3) y.a_scale = norm_a_scale(n.gmax, n.bmax, (x.rows / nb) * (int64_t)(x.c / groups));
-    if (wn) {
-      stats_pass(x, nb, eps, groups, wsb, stats, boff);
-      emit_wino(x, n, stats, y, nb, vd, vh, vw, groups, act, wn);
-      release(wsb);
-      release(stats);
-      return y;
-    }
-    if (wants_split16(x.rows, conv_gi)) {
-      y.half = true;
-      stats_pass(x, nb, eps, groups, wsb, stats, boff);
-      if (ok() && !dry) {
-        const int rows = (int)(x.rows / nb);
-        char* yh = reinterpret_cast<char*>(p(y));
-        chk(cs_groupnorm_apply_split16(p(x), p(stats), wf(n.g_off), wf(n.b_off), yh, yh + x.rows * x.c * 2, nb, rows, x.c,
-                                       x.c, x.c, groups, act, y.a_scale, status, st));
-      }
-      release(wsb);
-      release(stats);
-      return y;
-    }
-    if (boff >= 0) {       // bound wanted: statistics (+ bound) and apply as two launches (ops.py::groupnorm)
-      stats_pass(x, nb, eps, groups, wsb, stats, boff);
-      if (ok() && !dry)
-        chk(cs_groupnorm_apply(p(x), p(stats), wf(n.g_off), wf(n.b_off), p(y), nb, (int)(x.rows / nb), x.c, x.c, x.c, groups,
-                               act, st));
-    } else if (ok() && !dry) {
-      const int rows = (int)(x.rows / nb);
-      chk(cs_groupnorm(p(x), wf(n.g_off), wf(n.b_off), p(y), nb, rows, x.c, x.c, x.c, groups, eps, act, p(wsb), p(stats), st));
-    }
-    release(wsb);
-    release(stats);
-    return y;
-  }
-  Buf layernorm(const Buf& x, int ni) {
-    const Norm& n = pl.norms[ni];
-    Buf y = alloc(x.rows, x.c);
-    if (pl.math == CS_MATH_F16X3) y.a_scale = norm_a_scale(n.gmax, n.bmax, x.c);
-    // LayerNorm outputs only ever feed GEMMs: in F16X3 mode they are written as the interleaved operand pair
-    // (ops.py::layernorm pair_scale; CS_NO_PAIR16=1 keeps fp32 for A/B runs)
-    if (pl.math == CS_MATH_F16X3 && !cs_debug()->no_pair16 && x.c % 16 == 0) {
-      y.pair = true;
-      if (ok() && !dry)
-        chk(cs_layernorm_pair16(p(x), wf(n.g_off), wf(n.b_off), p(y), (int)x.rows, x.c, x.c, x.c, 1e-5f, y.a_scale,
-                                status, st));
-      return y;
-    }
-    if (ok() && !dry) chk(cs_layernorm(p(x), wf(n.g_off), wf(n.b_off), p(y), (int)x.rows, x.c, x.c, x.c, 1e-5f, st));
-    return y;
+    release(img);
   }
 };
 

@@ -26,21 +26,23 @@ struct Layer {
   int n[4];
   int emb_lo = 0;      // RES: column offset into the batched emb_layers projection
   // RES of an output block whose skip half is shared by the guidance halves (unet.py::_pack "channel-split ResBlocks"):
-  // split channel ks (> 0), channels of h, and the GEMMs {in_layers.2 h, in_layers.2 s, skip_connection h, skip_connection s}
+  // split channel ks (> 0), channels of h, and in_layers.2 as two GEMMs {over channels [0, ks), over channels [ks, C)}; the
+  // 1x1x1 skip_connection stays whole
   int ks = 0, ch_h = 0;
-  int gsp[4] = {-1, -1, -1, -1};
+  int gsp[2] = {-1, -1};
   int ctx_off = 0;     // ATTN: column offset into the context-vector block
   bool fused_geglu = false;
-  // ATTN, F16X3 (r5): what bounds the operands born inside the transformer block (cs_transformer_static_scales): filled by
-  // cs_unet_pack from the raw weights; ctx_max = the largest |entry| of the block's cross-attention row vector of the
-  // current run (cs_unet_set_context_bounds), 0 until the host sets it
+  // ATTN / ATTNBLOCK, F16X3: first of this block's float slots (34 / 4) behind the plan's |w| maxima, where cs_unet_pack
+  // leaves the statistics of the raw weights that bound the operands born inside the block
+  int stat_slot = -1;
+  // ATTN: those statistics (cs_transformer_static_scales); ctx_max = the largest |entry| of the block's cross-attention
+  // row vector of the current run (cs_unet_set_context_bounds), 0 until the host sets it
   CsTransformerStats ts;
   bool has_ts = false;
   float ctx_max = 0.f;
-  int ts_slot = -1;    // first of this block's 34 float slots behind the plan's |w| maxima
-  // ATTNBLOCK, F16X3 (r6): max row 2-norm of the fused qkv weight and max |bias| (cs_attnblock_static_scales), filled by
-  // cs_unet_pack; ab_slot = the block's 4 float slots, ab_w / ab_b = the raw parameters
-  int ab_slot = -1, ab_w = -1, ab_b = -1;
+  // ATTNBLOCK: max row 2-norm of the fused qkv weight and max |bias| (cs_attnblock_static_scales); ab_w / ab_b = the raw
+  // parameters they are taken from
+  int ab_w = -1, ab_b = -1;
   float ab_l2max = 0.f, ab_bmax = 0.f;
 };
 
@@ -56,6 +58,22 @@ struct cs_unet : Plan {
 };
 
 namespace {
+
+// every layer in block order: input blocks, middle, output blocks (U = cs_unet or const cs_unet)
+template <class U, class F>
+void for_each_layer(U& u, F&& fn) {
+  for (auto& layers : u.inp)
+    for (auto& l : layers) fn(l);
+  for (auto& l : u.mid) fn(l);
+  for (auto& layers : u.out)
+    for (auto& l : layers) fn(l);
+}
+
+bool has_attn(const std::vector<Layer>& layers) {
+  for (const Layer& l : layers)
+    if (l.kind == ATTN || l.kind == ATTNBLOCK) return true;
+  return false;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // plan construction (mirrors unet.py::unet_blocks / unet_param_shapes / DiffusionUNet._pack)
@@ -252,12 +270,7 @@ int build(cs_unet& u) {
   // split point as unet.py::_pack.
   if (c.use_spatial_transformer && !cs_debug()->no_cfg_split) {
     size_t n_prefix = 0;
-    while (n_prefix < u.inp.size()) {
-      bool attn = false;
-      for (const Layer& l : u.inp[n_prefix]) attn |= (l.kind == ATTN || l.kind == ATTNBLOCK);
-      if (attn) break;
-      ++n_prefix;
-    }
+    while (n_prefix < u.inp.size() && !has_attn(u.inp[n_prefix])) ++n_prefix;
     for (size_t j = 0; j < u.out.size(); ++j) {
       const size_t src = u.inp.size() - 1 - j;
       Layer& l = u.out[j][0];
@@ -271,13 +284,12 @@ int build(cs_unet& u) {
           break;
         }
       if (!ks || (C - ks) % 16) continue;
-      for (int which = 0; which < 1; ++which) {          // in_layers.2 (3x3x3); the 1x1x1 skip_connection stays whole
-        const int gi = l.g[which == 0 ? 0 : 2];
-        const int wp = u.gemms[gi].w[0].param, bp = u.gemms[gi].b.empty() ? -1 : u.gemms[gi].b[0].param;
-        const int k = u.gemms[gi].k;     // (the unsplit GEMM stays packed: small batches take it, see split_min_rows)
-        l.gsp[2 * which] = add_gemm_cin_range(u, wp, bp, l.cout, C, k, 0, ks);
-        l.gsp[2 * which + 1] = add_gemm_cin_range(u, wp, -1, l.cout, C, k, ks, C);
-      }
+      // in_layers.2 (3x3x3) as two GEMMs; the unsplit one stays packed: small batches take it, see split_min_rows
+      const int gi = l.g[0];
+      const int wp = u.gemms[gi].w[0].param, bp = u.gemms[gi].b.empty() ? -1 : u.gemms[gi].b[0].param;
+      const int k = u.gemms[gi].k;
+      l.gsp[0] = add_gemm_cin_range(u, wp, bp, l.cout, C, k, 0, ks);
+      l.gsp[1] = add_gemm_cin_range(u, wp, -1, l.cout, C, k, ks, C);
       l.ks = ks;
       l.ch_h = ch_h;
     }
@@ -290,41 +302,20 @@ int build(cs_unet& u) {
   u.g_emb_all = add_gemm(u, emb.w, emb.b, emb.total, ted, 0);
   u.emb_total = emb.total;
 
-  {
-    // r5: 34 float slots per transformer block for the static-bound statistics (cs_unet_pack); r6: 4 per AttentionBlock
-    int nblk = 0, nab = 0;
-    auto count = [&](std::vector<Layer>& layers) {
-      for (Layer& l : layers) {
-        if (l.kind == ATTN) ++nblk;
-        if (l.kind == ATTNBLOCK) ++nab;
-      }
-    };
-    for (auto& layers : u.inp) count(layers);
-    count(u.mid);
-    for (auto& layers : u.out) count(layers);
-    u.extra_slots = (c.math == CS_MATH_F16X3) ? 34 * nblk + 4 * nab : 0;
-  }
+  // F16X3: 34 float slots per transformer block for the static-bound statistics (cs_unet_pack), then 4 per AttentionBlock
+  int nblk = 0, nab = 0;
+  for_each_layer(u, [&](const Layer& l) {
+    nblk += l.kind == ATTN;
+    nab += l.kind == ATTNBLOCK;
+  });
+  u.extra_slots = (c.math == CS_MATH_F16X3) ? 34 * nblk + 4 * nab : 0;
   layout_arena(u);
   if (u.extra_slots) {
-    int k = 0;
-    auto assign = [&](std::vector<Layer>& layers) {
-      for (Layer& l : layers)
-        if (l.kind == ATTN) l.ts_slot = u.extra_slot0 + 34 * k++;
-    };
-    for (auto& layers : u.inp) assign(layers);
-    assign(u.mid);
-    for (auto& layers : u.out) assign(layers);
-    int k2 = 34 * k;                      // (the AttentionBlocks' slots follow the transformer blocks')
-    auto assign2 = [&](std::vector<Layer>& layers) {
-      for (Layer& l : layers)
-        if (l.kind == ATTNBLOCK) {
-          l.ab_slot = u.extra_slot0 + k2;
-          k2 += 4;
-        }
-    };
-    for (auto& layers : u.inp) assign2(layers);
-    assign2(u.mid);
-    for (auto& layers : u.out) assign2(layers);
+    int k = 0, k2 = 0;
+    for_each_layer(u, [&](Layer& l) {
+      if (l.kind == ATTN) l.stat_slot = u.extra_slot0 + 34 * k++;
+      if (l.kind == ATTNBLOCK) l.stat_slot = u.extra_slot0 + 34 * nblk + 4 * k2++;
+    });
   }
   return CS_OK;
 }
@@ -335,29 +326,27 @@ struct Exec : ExecBase {
       : ExecBase(u_, arena_, ws_, ws_bytes_, dry_, st_), u(u_) {}
   int64_t in_bound_off = -1;      // bound slot of the latent (conv_in's operand), set by forward()
 
+  // unet.py::_res
   Act res_block(const Layer& l, const Act& x, const Buf& semb) {
     const int rows = x.d * x.h * x.w;
-    // (xb: the skip conv below reads x RAW -- the GroupNorm's finalize kernel leaves x's magnitude bound on the way)
+    const bool own_skip = l.g[2] >= 0;
+    // xb: the skip conv below reads x RAW -- the GroupNorm's finalize kernel leaves x's magnitude bound on the way.
+    // x.d, x.h, x.w: where the conv takes the Winograd-W route the GroupNorm emits that operand
     int64_t xb = -1;
-    // (x.d, x.h, x.w: where the conv takes the Winograd-W route the GroupNorm emits that operand, unet.py::_res)
-    Buf hn = groupnorm(x.b, l.n[0], x.nb, 1e-5f, CS_ACT_SILU, 32, l.g[0], l.g[2] >= 0 ? &xb : nullptr, x.d, x.h, x.w);
-    // (want_stats: the conv's epilogue leaves the partial sums the next GroupNorm takes its statistics from -- unet.py::_res)
-    Buf h1 = gemm(hn, l.g[0], x.nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, dry ? nullptr : p(semb) + l.emb_lo, semb.c, rows,
-                  nullptr, 0, 0, 1, 0, /*want_stats=*/true);
+    Buf hn = groupnorm(x.b, l.n[0], x.nb, 1e-5f, CS_ACT_SILU, 32, l.g[0], own_skip ? &xb : nullptr, x.d, x.h, x.w);
+    // stats(): the conv's epilogue leaves the partial sums the next GroupNorm takes its statistics from
+    Buf h1 = gemm(hn, l.g[0], x.nb, x.d, x.h, x.w, GemmOpts().row_vector(at(semb, l.emb_lo), semb.c, rows).stats());
     release(hn);
     Buf hn2 = groupnorm(h1, l.n[1], x.nb, 1e-5f, CS_ACT_SILU, 32, l.g[1], nullptr, x.d, x.h, x.w);
     release(h1);
+    // the skip conv reads the RAW residual stream: operand scale from the tensor's actual range (x_bound=)
     Buf skip;
-    const bool own_skip = l.g[2] >= 0;
-    // (the skip conv reads the RAW residual stream: operand scale from the tensor's actual range, unet.py::_res x_bound=)
-    if (own_skip)
-      skip = gemm(x.b, l.g[2], x.nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, 0, false, 0.f, xb);
+    if (own_skip) skip = gemm(x.b, l.g[2], x.nb, x.d, x.h, x.w, GemmOpts().bound(xb));
     Act o = x;
     const Buf& sk = own_skip ? skip : x.b;
-    o.b = gemm(hn2, l.g[1], x.nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(sk), sk.c, 0, 1, 0,
-               /*want_stats=*/true);
+    o.b = gemm(hn2, l.g[1], x.nb, x.d, x.h, x.w, GemmOpts().residual(sk, sk.c).stats());
     release(hn2);
-    if (own_skip) release(skip);
+    release(skip);
     return o;
   }
 
@@ -374,58 +363,48 @@ struct Exec : ExecBase {
       chk(CS_EINVAL);
       return o;
     }
-    const int64_t m_launch = (int64_t)nbs * rows;
-    int64_t xb = -1;
-    Buf stats = gn_stats(x.b, nb, 1e-5f, 32, &xb);
-    const float* xs = dry ? nullptr : p(sk.b) + off;           // the shared channels of the skip tensor
-    // r5: where the halves' convs take the Winograd-W route (each launch covers nbs samples) their operands are emitted in
-    // that form -- the h half once per guidance half (unet.py::_res_split)
-    const int wn_h = wants_wino(l.gsp[0], nbs, x.d, x.h, x.w), wn_s = wants_wino(l.gsp[1], nbs, x.d, x.h, x.w);
-    Buf a_h;
-    if (!wn_h)
-      a_h = gn_apply_range(dry ? nullptr : p(x.b), C, x.b.rows, nb, stats, l.n[0], 32, cpg, 0, ks, CS_ACT_SILU, l.gsp[0],
-                           m_launch);
-    Buf a_s = gn_apply_range(xs, ch_s, sk.b.rows, nbs, stats, l.n[0], 32, cpg, ks, cs, CS_ACT_SILU, l.gsp[1], m_launch,
-                             wn_s, x.d, x.h, x.w);
-    auto lo_of = [&](const Buf& b) -> const void* {            // lo image of a pre-split pair / of a Winograd-W operand
-      return ((b.half || b.wino) && !dry) ? reinterpret_cast<const char*>(p(b)) + b.rows * b.c * 2 : nullptr;
+    // GroupNorm ranges: the statistics of the whole concatenation once (+ its magnitude bound for the skip conv), then
+    // channels [ch0, ch0 + c) of nbr samples from sample0 on, read at xp with row stride ldx, in the form conv_gi wants
+    // for a launch over nbs samples (wn: wants_wino's answer)
+    const Norm& n0 = pl.norms[l.n[0]];
+    GnStats s = gn_stats_alloc(x.b, nb, 32, true);
+    gn_stats_run(x.b, nb, 1e-5f, 32, s);
+    release(s.wsb);
+    auto gn_range = [&](const float* xp, int ldx, int nbr, int64_t sample0, int ch0, int c, int conv_gi, int wn) {
+      Buf y = gn_out(n0, (int64_t)nbr * rows, c, nbr, cpg, wn, conv_gi, (int64_t)nbs * rows);
+      gn_emit(xp, ldx, at(s.stats, sample0 * 32 * 2), n0, y, nbr, rows, x.d, x.h, x.w, 32, cpg, ch0, CS_ACT_SILU);
+      return y;
     };
+    const int wn_h = wants_wino(l.gsp[0], nbs, x.d, x.h, x.w), wn_s = wants_wino(l.gsp[1], nbs, x.d, x.h, x.w);
+    // the h channels [0, ks): one operand for the whole batch -- the Winograd-W form is emitted per guidance half instead
+    Buf a_h;
+    if (!wn_h) a_h = gn_range(at(x.b), C, nb, 0, 0, ks, l.gsp[0], 0);
+    // shared half: the skip channels [ks, C), read from the skip tensor itself, through their GEMM at batch nbs
+    Buf a_s = gn_range(at(sk.b, off), ch_s, nbs, 0, ks, cs, l.gsp[1], wn_s);
     Buf y_s = alloc(sk.b.rows, cout);
-    if (ok()) gemm_view(dry ? nullptr : p(a_s), (a_s.half || a_s.wino) ? (dry ? (const void*)1 : lo_of(a_s)) : nullptr, cs,
-                        l.gsp[1], nbs, x.d, x.h, x.w, dry ? nullptr : p(y_s), cout, nullptr, 0, 1, nullptr, 0, a_s.a_scale,
-                        a_s.wino);
+    if (ok()) gemm_view(view(a_s), l.gsp[1], nbs, x.d, x.h, x.w, at(y_s), cout);
     release(a_s);
+    // per-guidance-half GEMMs over the h channels: + the half's emb row vectors, + the shared half as the residual
     Buf h1 = alloc(x.b.rows, cout);
     for (int g = 0; g < nb / nbs && ok(); ++g) {
-      const int64_t r0 = (int64_t)g * nbs * rows;
-      const float* rv = dry ? nullptr : p(semb) + (int64_t)g * nbs * semb.c + l.emb_lo;
+      const int64_t s0 = (int64_t)g * nbs, r0 = s0 * rows;
+      GemmOpts opt;
+      opt.row_vector(at(semb, s0 * semb.c + l.emb_lo), semb.c, rows).residual(y_s, cout);
       if (wn_h) {
-        Buf a_g = gn_apply_range(dry ? nullptr : p(x.b) + r0 * C, C, (int64_t)nbs * rows, nbs, stats, l.n[0], 32, cpg, 0, ks,
-                                 CS_ACT_SILU, l.gsp[0], m_launch, wn_h, x.d, x.h, x.w, (int64_t)g * nbs);
-        if (ok()) gemm_view(dry ? nullptr : p(a_g), dry ? (const void*)1 : lo_of(a_g), ks, l.gsp[0], nbs, x.d, x.h, x.w,
-                            dry ? nullptr : p(h1) + r0 * cout, cout, rv, semb.c, rows, dry ? nullptr : p(y_s), cout,
-                            a_g.a_scale, a_g.wino);
+        Buf a_g = gn_range(at(x.b, r0 * C), C, nbs, s0, 0, ks, l.gsp[0], wn_h);
+        if (ok()) gemm_view(view(a_g), l.gsp[0], nbs, x.d, x.h, x.w, at(h1, r0 * cout), cout, opt);
         release(a_g);
-        continue;
+      } else {
+        gemm_view(view(a_h, r0), l.gsp[0], nbs, x.d, x.h, x.w, at(h1, r0 * cout), cout, opt);
       }
-      const float* ah = nullptr;
-      const void* al = a_h.half ? (const void*)1 : nullptr;
-      if (!dry) {
-        // fp32: rows of ks floats; pre-split: two fp16 images of ks halves per row
-        ah = a_h.half ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p(a_h)) + r0 * ks * 2) : p(a_h) + r0 * ks;
-        if (a_h.half) al = reinterpret_cast<const char*>(lo_of(a_h)) + r0 * ks * 2;
-      }
-      gemm_view(ah, al, ks, l.gsp[0], nbs, x.d, x.h, x.w, dry ? nullptr : p(h1) + r0 * cout, cout, rv, semb.c, rows,
-                dry ? nullptr : p(y_s), cout, a_h.a_scale);
     }
-    release(stats);
-    if (!wn_h) release(a_h);
+    release(s.stats);
+    release(a_h);
     release(y_s);
-    Buf skc = gemm(x.b, l.g[2], nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, 0, false, 0.f, xb);
+    Buf skc = gemm(x.b, l.g[2], nb, x.d, x.h, x.w, GemmOpts().bound(s.bound));
     Buf hn2 = groupnorm(h1, l.n[1], nb, 1e-5f, CS_ACT_SILU, 32, l.g[1], nullptr, x.d, x.h, x.w);
     release(h1);
-    o.b = gemm(hn2, l.g[1], nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(skc), cout, 0, 1, 0,
-               /*want_stats=*/true);
+    o.b = gemm(hn2, l.g[1], nb, x.d, x.h, x.w, GemmOpts().residual(skc, cout).stats());
     release(hn2);
     release(skc);
     return o;
@@ -442,7 +421,7 @@ struct Exec : ExecBase {
     Buf qkv = linear(n1, l.g[1]);
     release(n1);
     Buf a = alloc(rows, c);
-    // r5: static bounds of the operands born inside the block (unet.py::_static_scales; the ONE rule in cs_plan.hip)
+    // static bounds of the operands born inside the block (unet.py::_static_scales; the ONE rule in cs_plan.hip)
     float ss[12];
     const Norm& gnn = pl.norms[l.n[0]];
     const bool stat = l.has_ts && u.cfg.math == CS_MATH_F16X3 && !cs_debug()->no_static_scales && ctxvec &&
@@ -451,8 +430,7 @@ struct Exec : ExecBase {
     if (stat) a.a_scale = ss[3];
     release(qkv);
     // one context token: attn2(x) == to_out(to_v(ctx)) for every query row -> a row vector in this epilogue
-    Buf t1 = linear(a, l.g[2], CS_ACT_NONE, ctxvec ? ctxvec + l.ctx_off : nullptr, u.ctx_total, n,
-                    dry ? nullptr : p(t0), c);
+    Buf t1 = linear(a, l.g[2], GemmOpts().row_vector(ctxvec ? ctxvec + l.ctx_off : nullptr, u.ctx_total, n).residual(t0, c));
     release(a);
     release(t0);
     Buf n3 = layernorm(t1, l.n[3]);
@@ -462,7 +440,7 @@ struct Exec : ExecBase {
     const float pairs = u.cfg.math == CS_MATH_F16X3 ? 16.f : 0.f;
     const float pair_gg = (pairs > 0.f && stat) ? ss[4] : pairs, pair_t2 = (pairs > 0.f && stat) ? ss[5] : pairs;
     if (l.fused_geglu) {
-      gg = linear(n3, l.g[5], CS_ACT_GEGLU, nullptr, 0, 1, nullptr, 0, 0, pair_gg);   // tile 0: a 224-column tile for the gate
+      gg = linear(n3, l.g[5], GemmOpts().activation(CS_ACT_GEGLU).pair(pair_gg));   // tile 0: a 224-column tile for the gate
     } else {
       Buf ff = linear(n3, l.g[5]);
       gg = alloc(rows, 4 * c);
@@ -471,14 +449,13 @@ struct Exec : ExecBase {
     }
     if (stat && !gg.pair) gg.a_scale = ss[4];      // (a producer that could not emit the pair hands over fp32)
     release(n3);
-    Buf t2 = linear(gg, l.g[6], CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(t1), c, 0, pair_t2);
+    Buf t2 = linear(gg, l.g[6], GemmOpts().residual(t1, c).pair(pair_t2));
     if (stat && !t2.pair) t2.a_scale = ss[5];
     release(gg);
     release(t1);
     Act o = x;
     // (x.nb samples of n tokens: what the epilogue's GroupNorm partial sums are tiled by -- unet.py::_attn, spatial=)
-    o.b = gemm(t2, l.g[7], x.nb, n, 1, 1, 1, 0, CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(x.b), c, 0, 1, 0,
-               /*want_stats=*/true);
+    o.b = gemm(t2, l.g[7], x.nb, n, 1, 1, GemmOpts().residual(x.b, c).stats());
     release(t2);
     return o;
   }
@@ -491,7 +468,7 @@ struct Exec : ExecBase {
     Buf qkv = linear(xn, l.g[0]);
     release(xn);
     Buf a = alloc(rows, c);
-    // r6: static operand scales of q / k / v and of the attention output (unet.py::_attnblock: the same rule and statistics)
+    // static operand scales of q / k / v and of the attention output (unet.py::_attnblock: the same rule and statistics)
     float ss[4];
     const float qks = (float)std::pow((double)dh, -0.5);
     const bool stat = attnblock_scales(l.n[0], (int64_t)n * (c / 32), c, l.ab_l2max, l.ab_bmax, qks, ss);
@@ -499,8 +476,7 @@ struct Exec : ExecBase {
     if (stat) a.a_scale = ss[3];
     release(qkv);
     Act o = x;
-    o.b = gemm(a, l.g[1], x.nb, n, 1, 1, 1, 0, CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(x.b), c, 0, 1, 0,
-               /*want_stats=*/true);
+    o.b = gemm(a, l.g[1], x.nb, n, 1, 1, GemmOpts().residual(x.b, c).stats());
     release(a);
     return o;
   }
@@ -521,8 +497,7 @@ struct Exec : ExecBase {
       switch (l.kind) {
         case CONV_IN:
           o = h;
-          o.b = gemm(h.b, l.g[0], h.nb, h.d, h.h, h.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, 0, true, 0.f,
-                     in_bound_off);
+          o.b = gemm(h.b, l.g[0], h.nb, h.d, h.h, h.w, GemmOpts().stats().bound(in_bound_off));
           break;
         case RES:
           o = res_block(l, h, semb);
@@ -537,8 +512,7 @@ struct Exec : ExecBase {
           const int sd = u.cfg.dims == 3 ? 1 : 2;
           o = h;
           // (Down / Upsample read the RAW stream with no GroupNorm in front: its bound from the producers' partials)
-          o.b = gemm(h.b, l.g[0], h.nb, h.d, h.h, h.w, 2, 0, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, sd, 0, true, 0.f,
-                     range_bound(h.b, h.nb));
+          o.b = gemm(h.b, l.g[0], h.nb, h.d, h.h, h.w, GemmOpts().stride(2, sd).stats().bound(range_bound(h.b, h.nb)));
           o.d = h.d / sd;
           o.h = h.h / 2;
           o.w = h.w / 2;
@@ -547,8 +521,7 @@ struct Exec : ExecBase {
         case UP: {     // nearest x2 folded into the conv's addressing (openai_model_3d.py:148-157)
           const int ud = u.cfg.dims == 3 ? 0 : 1;
           o = h;
-          o.b = gemm(h.b, l.g[0], h.nb, h.d, h.h, h.w, 1, 1, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, ud, true, 0.f,
-                     range_bound(h.b, h.nb));
+          o.b = gemm(h.b, l.g[0], h.nb, h.d, h.h, h.w, GemmOpts().upsample(1, ud).stats().bound(range_bound(h.b, h.nb)));
           o.d = h.d << ud;
           o.h = h.h * 2;
           o.w = h.w * 2;
@@ -578,12 +551,6 @@ struct Exec : ExecBase {
   }
 };
 
-bool has_attn(const std::vector<Layer>& layers) {
-  for (const Layer& l : layers)
-    if (l.kind == ATTN || l.kind == ATTNBLOCK) return true;
-  return false;
-}
-
 int forward(Exec& e, const float* x_ncdhw, const int64_t* t, const float* ctxvec, float* eps_ncdhw, int nbx,
             int cfg_pairs) {
   const cs_unet& u = e.u;
@@ -593,10 +560,10 @@ int forward(Exec& e, const float* x_ncdhw, const int64_t* t, const float* ctxvec
   e.amax_begin(64);       // magnitude-bound slots of this forward (unet.py::forward_ndhwc: self._amax)
   Buf temb = e.alloc(nbx, c.model_channels);
   if (e.ok() && !e.dry) e.chk(cs_timestep_embedding(t, e.p(temb), nbx, c.model_channels, 10000.0f, e.st));
-  Buf e1 = e.linear(temb, u.g_te0, CS_ACT_SILU);
+  Buf e1 = e.linear(temb, u.g_te0, GemmOpts().activation(CS_ACT_SILU));
   e.release(temb);
   // every consumer of `emb` is emb_layers = SiLU -> Linear (openai_model_3d.py:257-263): keep SiLU(emb)
-  Buf e2 = e.linear(e1, u.g_te2, CS_ACT_SILU);
+  Buf e2 = e.linear(e1, u.g_te2, GemmOpts().activation(CS_ACT_SILU));
   e.release(e1);
   Buf semb = e.linear(e2, u.g_emb_all);
   e.release(e2);
@@ -604,7 +571,7 @@ int forward(Exec& e, const float* x_ncdhw, const int64_t* t, const float* ctxvec
   h.nb = nbx; h.d = c.d; h.h = c.h; h.w = c.w;
   h.b = e.alloc((int64_t)nbx * S, u.cpad_in);
   if (e.ok() && !e.dry) e.chk(cs_nchw_to_ndhwc(x_ncdhw, e.p(h.b), nbx, c.in_channels, S, u.cpad_in, e.st));
-  // r6: conv_in reads the RAW latent -- its exact max |.| goes to a bound slot (unet.py::forward_ndhwc: ops.absmax_bound)
+  // conv_in reads the RAW latent -- its exact max |.| goes to a bound slot (unet.py::forward_ndhwc: ops.absmax_bound)
   e.in_bound_off = e.amax_slot();
   if (e.in_bound_off >= 0 && e.ok() && !e.dry)
     e.chk(cs_absmax(e.p(h.b), (int64_t)nbx * S * u.cpad_in, e.bound_ptr(e.in_bound_off), e.st));
@@ -720,120 +687,97 @@ extern "C" int64_t cs_unet_context_floats(const cs_unet* u) { return u ? u->ctx_
 extern "C" int cs_unet_pack(cs_unet* u, const void* raw_dev, void* arena_dev, cs_stream_t stream) {
   const int rc = pack_plan(u, raw_dev, arena_dev, stream);
   if (rc != CS_OK || !u || u->math != CS_MATH_F16X3) return rc;
-  {
-    // r6: every AttentionBlock's static-bound statistics (unet.py::_pack: the same kernel on the same tensors, the same values):
-    // {max row 2-norm, max |.|} of the fused qkv weight into slots 0-1, of its bias into slots 2-3; one read-back
-    hipStream_t st0 = (hipStream_t)stream;
-    const char* raw0 = reinterpret_cast<const char*>(raw_dev);
-    float* d0 = reinterpret_cast<float*>(reinterpret_cast<char*>(arena_dev) + u->amax_off);
-    std::vector<Layer*> abs_;
-    auto collect_ab = [&](std::vector<Layer>& layers) {
-      for (Layer& l : layers)
-        if (l.kind == ATTNBLOCK && l.ab_slot >= 0) abs_.push_back(&l);
-    };
-    for (auto& layers : u->inp) collect_ab(layers);
-    collect_ab(u->mid);
-    for (auto& layers : u->out) collect_ab(layers);
-    for (Layer* lp : abs_) {
-      const int c3 = 3 * lp->cin;
-      int r2 = cs_weight_rowstats(reinterpret_cast<const float*>(raw0 + u->params[lp->ab_w].raw_off), c3, lp->cin, d0 + lp->ab_slot,
-                                  stream);
-      if (r2 == CS_OK)
-        r2 = cs_weight_rowstats(reinterpret_cast<const float*>(raw0 + u->params[lp->ab_b].raw_off), 1, c3, d0 + lp->ab_slot + 2,
-                                stream);
-      if (r2 != CS_OK) return r2;
-    }
-    if (!abs_.empty()) {
-      std::vector<float> host0(4 * abs_.size());
-      if (hipMemcpyAsync(host0.data(), d0 + abs_[0]->ab_slot, host0.size() * 4, hipMemcpyDeviceToHost, st0) != hipSuccess ||
-          hipStreamSynchronize(st0) != hipSuccess)
-        return CS_EINVAL;
-      for (size_t i = 0; i < abs_.size(); ++i) {
-        abs_[i]->ab_l2max = host0[4 * i];
-        abs_[i]->ab_bmax = host0[4 * i + 3];
-      }
-    }
-  }
-  if (!u->cfg.use_spatial_transformer) return rc;
-  // r5: the static-bound statistics of every transformer block (unet.py::_pack: the same kernel, the same values) -- row
-  // 2-norm maxima and |.| maxima of the block's Linears and LayerNorm parameters; 34 float slots per block behind the
-  // plan's |w| maxima (zeroed by pack_plan), ONE more read-back at load time
+  // The static-bound statistics of every AttentionBlock, then of every transformer block (unet.py::_pack: the same kernel
+  // on the same tensors, the same values): cs_weight_rowstats leaves {max row 2-norm, max |.|} of one raw tensor per job
+  // in two of the block's float slots behind the plan's |w| maxima (zeroed by pack_plan).  ONE read-back per block kind at
+  // load time; a model has one kind
   hipStream_t st = (hipStream_t)stream;
   const char* raw = reinterpret_cast<const char*>(raw_dev);
   float* d_amax = reinterpret_cast<float*>(reinterpret_cast<char*>(arena_dev) + u->amax_off);
   auto src = [&](int param) { return reinterpret_cast<const float*>(raw + u->params[param].raw_off); };
-  std::vector<Layer*> blocks;
-  auto collect = [&](std::vector<Layer>& layers) {
-    for (Layer& l : layers)
-      if (l.kind == ATTN && l.ts_slot >= 0) blocks.push_back(&l);
+  struct Job {
+    const float* w;
+    int rows, cols;
   };
-  for (auto& layers : u->inp) collect(layers);
-  collect(u->mid);
-  for (auto& layers : u->out) collect(layers);
-  if (blocks.empty()) return rc;
-  for (Layer* lp : blocks) {
-    const Layer& l = *lp;
-    const int c = l.cin;
-    float* o = d_amax + l.ts_slot;
-    const Gemm& qkv = u->gemms[l.g[1]];
-    const Gemm& to = u->gemms[l.g[2]];
-    const Gemm& ff = u->gemms[l.g[5]];
-    const Gemm& f2 = u->gemms[l.g[6]];
-    const Gemm& pi = u->gemms[l.g[0]];
-    const Norm& n1 = u->norms[l.n[1]];
-    const Norm& n3 = u->norms[l.n[3]];
-    if (qkv.w.size() != 3 || to.w.empty() || to.b.empty() || ff.w.empty() || ff.b.empty() || f2.w.empty() || f2.b.empty() ||
-        pi.w.empty() || pi.b.empty())
-      return CS_EINVAL;
-    const float* wff = src(ff.w[0].param);
-    const float* bff = src(ff.b[0].param);
-    struct Job { const float* w; int rows, cols; };
-    const Job jobs[17] = {
-        {src(qkv.w[0].param), c, c}, {src(qkv.w[1].param), c, c}, {src(qkv.w[2].param), c, c},        // rq rk rv
-        {src(to.w[0].param), c, c}, {src(to.b[0].param), 1, c},                                          // ro bo
-        {wff, 4 * c, c}, {bff, 1, 4 * c}, {wff + (int64_t)4 * c * c, 4 * c, c}, {bff + 4 * c, 1, 4 * c},  // rx bx rg bg
-        {src(f2.w[0].param), c, 4 * c}, {src(f2.b[0].param), 1, c},                                      // r2 b2
-        {src(pi.w[0].param), c, c}, {src(pi.b[0].param), 1, c},                                          // rpi bpi
-        {src(n1.gp), 1, c}, {src(n1.bp), 1, c}, {src(n3.gp), 1, c}, {src(n3.bp), 1, c}};                 // g1 be1 g3 be3
-    for (int j = 0; j < 17; ++j) {
-      const int r2 = cs_weight_rowstats(jobs[j].w, jobs[j].rows, jobs[j].cols, o + 2 * j, stream);
-      if (r2 != CS_OK) return r2;
+  for (Kind kind : {ATTNBLOCK, ATTN}) {
+    std::vector<Layer*> blocks;
+    for_each_layer(*u, [&](Layer& l) {
+      if (l.kind == kind && l.stat_slot >= 0) blocks.push_back(&l);
+    });
+    if (blocks.empty()) continue;
+    const int njobs = kind == ATTN ? 17 : 2;      // two float slots each
+    for (const Layer* lp : blocks) {
+      const Layer& l = *lp;
+      const int c = l.cin;
+      std::vector<Job> jobs;
+      if (kind == ATTNBLOCK) {      // the fused qkv weight [3c][c] and its bias
+        jobs = {{src(l.ab_w), 3 * c, c}, {src(l.ab_b), 1, 3 * c}};
+      } else {      // the block's Linears and LayerNorm parameters
+        const Gemm& qkv = u->gemms[l.g[1]];
+        const Gemm& to = u->gemms[l.g[2]];
+        const Gemm& ff = u->gemms[l.g[5]];
+        const Gemm& f2 = u->gemms[l.g[6]];
+        const Gemm& pi = u->gemms[l.g[0]];
+        const Norm& n1 = u->norms[l.n[1]];
+        const Norm& n3 = u->norms[l.n[3]];
+        if (qkv.w.size() != 3 || to.w.empty() || to.b.empty() || ff.w.empty() || ff.b.empty() || f2.w.empty() || f2.b.empty() ||
+            pi.w.empty() || pi.b.empty())
+          return CS_EINVAL;
+        const float* wff = src(ff.w[0].param);
+        const float* bff = src(ff.b[0].param);
+        jobs = {
+            {src(qkv.w[0].param), c, c}, {src(qkv.w[1].param), c, c}, {src(qkv.w[2].param), c, c},        // rq rk rv
+            {src(to.w[0].param), c, c}, {src(to.b[0].param), 1, c},                                          // ro bo
+            {wff, 4 * c, c}, {bff, 1, 4 * c}, {wff + (int64_t)4 * c * c, 4 * c, c}, {bff + 4 * c, 1, 4 * c},  // rx bx rg bg
+            {src(f2.w[0].param), c, 4 * c}, {src(f2.b[0].param), 1, c},                                      // r2 b2
+            {src(pi.w[0].param), c, c}, {src(pi.b[0].param), 1, c},                                          // rpi bpi
+            {src(n1.gp), 1, c}, {src(n1.bp), 1, c}, {src(n3.gp), 1, c}, {src(n3.bp), 1, c}};                 // g1 be1 g3 be3
+      }
+      if ((int)jobs.size() != njobs) return CS_EINVAL;
+      for (int j = 0; j < njobs; ++j) {
+        const int r2 = cs_weight_rowstats(jobs[j].w, jobs[j].rows, jobs[j].cols, d_amax + l.stat_slot + 2 * j, stream);
+        if (r2 != CS_OK) return r2;
+      }
     }
-  }
-  std::vector<float> host((size_t)34 * blocks.size());
-  // (the blocks' slots are contiguous: they were reserved one after the other)
-  if (hipMemcpyAsync(host.data(), d_amax + blocks[0]->ts_slot, host.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return CS_EINVAL;
-  for (size_t b = 0; b < blocks.size(); ++b) {
-    const float* h = host.data() + 34 * b;
-    // which of {row norm, abs max} each field takes (unet.py::_pack)
-    static const int which[17] = {0, 0, 0, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 1, 0, 1, 0};
-    float v[17];
-    for (int j = 0; j < 17; ++j) v[j] = h[2 * j + which[j]];
-    CsTransformerStats& t = blocks[b]->ts;
-    t.rq = v[0]; t.rk = v[1]; t.rv = v[2]; t.ro = v[3]; t.bo = v[4]; t.rx = v[5]; t.bx = v[6]; t.rg = v[7]; t.bg = v[8];
-    t.r2 = v[9]; t.b2 = v[10]; t.rpi = v[11]; t.bpi = v[12]; t.g1 = v[13]; t.be1 = v[14]; t.g3 = v[15]; t.be3 = v[16];
-    blocks[b]->has_ts = true;
+    // (the blocks' slots are contiguous: they were reserved one after the other)
+    std::vector<float> host((size_t)2 * njobs * blocks.size());
+    if (hipMemcpyAsync(host.data(), d_amax + blocks[0]->stat_slot, host.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return CS_EINVAL;
+    for (size_t b = 0; b < blocks.size(); ++b) {
+      const float* h = host.data() + 2 * njobs * b;
+      if (kind == ATTNBLOCK) {
+        blocks[b]->ab_l2max = h[0];      // the weight's row norm, the bias's abs max
+        blocks[b]->ab_bmax = h[3];
+        continue;
+      }
+      // which of {row norm, abs max} each field takes (unet.py::_pack)
+      static const int which[17] = {0, 0, 0, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 1, 0, 1, 0};
+      float v[17];
+      for (int j = 0; j < 17; ++j) v[j] = h[2 * j + which[j]];
+      CsTransformerStats& t = blocks[b]->ts;
+      t.rq = v[0]; t.rk = v[1]; t.rv = v[2]; t.ro = v[3]; t.bo = v[4]; t.rx = v[5]; t.bx = v[6]; t.rg = v[7]; t.bg = v[8];
+      t.r2 = v[9]; t.b2 = v[10]; t.rpi = v[11]; t.bpi = v[12]; t.g1 = v[13]; t.be1 = v[14]; t.g3 = v[15]; t.be3 = v[16];
+      blocks[b]->has_ts = true;
+    }
   }
   return CS_OK;
 }
 
-// r5: the largest |entry| of every transformer block's cross-attention row vector of the CURRENT run, in block order (input
+// the largest |entry| of every transformer block's cross-attention row vector of the CURRENT run, in block order (input
 // blocks, middle, output blocks) -- host data the caller reads back once per run after cs_unet_context (it enters t1's
 // static bound, cs_transformer_static_scales).  n must equal the number of transformer blocks; never called: 0 is assumed.
 extern "C" int cs_unet_set_context_bounds(cs_unet* u, const float* ctx_max, int n) {
   if (!u || !ctx_max || n < 0) return CS_EINVAL;
-  std::vector<Layer*> blocks;
-  auto collect = [&](std::vector<Layer>& layers) {
-    for (Layer& l : layers)
-      if (l.kind == ATTN) blocks.push_back(&l);
-  };
-  for (auto& layers : u->inp) collect(layers);
-  collect(u->mid);
-  for (auto& layers : u->out) collect(layers);
-  if ((int)blocks.size() != n) return CS_EINVAL;
-  for (int i = 0; i < n; ++i) blocks[i]->ctx_max = ctx_max[i] > 0.f ? ctx_max[i] : 0.f;
+  int nblk = 0;
+  for_each_layer(*u, [&](const Layer& l) { nblk += l.kind == ATTN; });
+  if (nblk != n) return CS_EINVAL;
+  int i = 0;
+  for_each_layer(*u, [&](Layer& l) {
+    if (l.kind != ATTN) return;
+    l.ctx_max = ctx_max[i] > 0.f ? ctx_max[i] : 0.f;
+    ++i;
+  });
   return CS_OK;
 }
 
@@ -854,58 +798,41 @@ extern "C" int cs_unet_context(const cs_unet* u, const void* arena, const float*
   if (!u || !u->packed || !arena || !ctx || !ctxvec || !workspace || nb_ctx <= 0) return CS_EINVAL;
   if (!u->cfg.use_spatial_transformer) return CS_EINVAL;      // the concat family has no context
   Exec e(*u, arena, workspace, workspace_bytes, false, (hipStream_t)stream);
+  e.status = status;
   const bool dyn = u->cfg.math == CS_MATH_F16X3 && !cs_debug()->no_dyn_scale && !cs_debug()->no_static_scales;
   Buf slots = e.alloc(64, 1);              // slot 0: max |ctx|; slot 1 + k: max |to_v(ctx)| of transformer block k
   int nslot = 0;
   if (dyn && e.ok() && hipMemsetAsync(e.p(slots), 0, 64 * 4, e.st) != hipSuccess) e.chk(CS_EINVAL);
-  // ctx rows are read in place: describe them as a buffer view at offset (ctx - workspace)
-  auto visit = [&](const Layer& l) {
+  for_each_layer(*u, [&](const Layer& l) {
     if (l.kind != ATTN || !e.ok()) return;
     const Gemm& gv = u->gemms[l.g[3]];
     const Gemm& go = u->gemms[l.g[4]];
     Buf v2 = e.alloc(nb_ctx, gv.cout);
     if (!e.ok()) return;
-    CsConvGemm q;
-    for (int pass = 0; pass < 2 && e.ok(); ++pass) {
+    for (int pass = 0; pass < 2 && e.ok(); ++pass) {      // to_v over the context rows (read in place), then to_out
       const Gemm& g = pass == 0 ? gv : go;
-      memset(&q, 0, sizeof(q));
-      // r5 (unet.py::_context_vectors): the context and to_v's output are raw operands -- their scale follows a device-side
+      View a;
+      a.x = pass == 0 ? ctx : e.p(v2);
+      a.lda = g.cin_pad;
+      GemmOpts opt;
+      // unet.py::_context_vectors: the context and to_v's output are raw operands -- their scale follows a device-side
       // magnitude bound (max |.| into a workspace slot, CsConvGemm.a_bound) instead of the constant 16
       if (dyn) {
-        const float* src = pass == 0 ? ctx : e.p(v2);
         const int64_t nel = (int64_t)nb_ctx * (pass == 0 ? u->cfg.context_dim : gv.cout);
-        float* slot = e.p(slots) + (pass == 0 ? 0 : 1 + nslot);
+        const int slot = pass == 0 ? 0 : 1 + nslot;
         if (pass == 1 || nslot == 0) {
-          CS_LAUNCH(absmax_kernel, dim3(cs_grid_for(nel, 256, 256)), dim3(256), 0, e.st, src, nel, slot);
+          CS_LAUNCH(absmax_kernel, dim3(cs_grid_for(nel, 256, 256)), dim3(256), 0, e.st, a.x, nel, e.p(slots) + slot);
           if (hipGetLastError() != hipSuccess) e.chk(CS_EINVAL);
         }
-        q.a_bound = slot;
+        opt.bound(slots.off + 4 * slot);
         if (pass == 1) ++nslot;
       }
-      q.x = pass == 0 ? ctx : e.p(v2);
-      q.out = pass == 0 ? e.p(v2) : ctxvec + l.ctx_off;
-      q.w = reinterpret_cast<const float*>(e.arena + g.w_off);
-      if (u->cfg.math == CS_MATH_F16X3) {
-        q.w_lo = e.arena + g.wlo_off;
-        q.acc_scale = g.acc_scale;
-        q.a_scale = 16.0f;
-      }
-      q.bias = g.b_off >= 0 ? e.wf(g.b_off) : nullptr;
-      q.nb = nb_ctx; q.din = q.hin = q.win = q.dout = q.hout = q.wout = 1;
-      q.cin = g.cin_pad; q.cout = g.cout;
-      q.lda = g.cin_pad; q.ldw = g.ldw; q.ldo = pass == 0 ? g.cout : u->ctx_total;
-      q.kd = q.kh = q.kw = 1; q.sd = q.sh = q.sw = 1;
-      q.rv_rows = 1; q.math = u->cfg.math;
-      q.status = status;
+      CsConvGemm q;
+      e.describe(q, g, a, pass == 0 ? e.p(v2) : ctxvec + l.ctx_off, pass == 0 ? g.cout : u->ctx_total, nb_ctx, 1, 1, 1, opt);
       e.chk(cs_conv_gemm(&q, e.st));
     }
     e.release(v2);
-  };
-  for (const auto& layers : u->inp)
-    for (const Layer& l : layers) visit(l);
-  for (const Layer& l : u->mid) visit(l);
-  for (const auto& layers : u->out)
-    for (const Layer& l : layers) visit(l);
+  });
   return e.rc;
 }
 

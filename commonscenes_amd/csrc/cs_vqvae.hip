@@ -33,7 +33,7 @@ struct cs_vqvae : Plan {
   std::vector<std::vector<ResP>> up;      // [level][block]
   std::vector<int> up_conv;               // [level] upsample conv GEMM or -1
   int block_in0 = 0, c_final = 0, grid = 0;
-  // r6: what bounds mid.attn_1's q / k / v (cs_attnblock_static_scales): max row 2-norm of the three 1x1x1 conv weights and
+  // what bounds mid.attn_1's q / k / v (cs_attnblock_static_scales): max row 2-norm of the three 1x1x1 conv weights and
   // max |bias|, filled by cs_vqvae_pack from the raw weights (F16X3 only; 0 = none: the constant scale 16)
   int p_qkv_w[3] = {-1, -1, -1}, p_qkv_b[3] = {-1, -1, -1};
   float attn_l2max = 0.f, attn_bmax = 0.f;
@@ -108,7 +108,7 @@ int build(cs_vqvae& u) {
     pb.push_back({-1, 0, zpad});
   }
   u.g_post = add_gemm(u, pw, pb, c.z_channels + zpad, c.embed_dim, 1);
-  u.extra_slots = c.math == CS_MATH_F16X3 ? 4 : 0;        // r6: the attention block's static-bound statistics (cs_vqvae_pack)
+  u.extra_slots = c.math == CS_MATH_F16X3 ? 4 : 0;        // the attention block's static-bound statistics (cs_vqvae_pack)
   layout_arena(u);
   return CS_OK;
 }
@@ -117,23 +117,22 @@ struct VExec : ExecBase {
   const cs_vqvae& u;
   VExec(const cs_vqvae& u_, const void* arena_, void* ws_, int64_t ws_bytes_, bool dry_, hipStream_t st_)
       : ExecBase(u_, arena_, ws_, ws_bytes_, dry_, st_), u(u_) {
-    stats_invariant_only = true;      // r5: GroupNorm partials only from batch-independent statistics tiles (vqvae.py)
+    stats_invariant_only = true;      // GroupNorm partials only from batch-independent statistics tiles (vqvae.py)
   }
 
   // ResnetBlock.forward (vqvae_modules.py:103-123): GN+swish -> conv -> GN+swish -> conv, + (1x1-projected) input
   Act res(const ResP& r, const Act& x) {
-    // (x.d, x.h, x.w, r5: the Winograd-W operand where the conv takes that route -- decided by the sample geometry, vqvae.py)
+    // (x.d, x.h, x.w: the Winograd-W operand where the conv takes that route -- decided by the sample geometry, vqvae.py)
     Buf h = groupnorm(x.b, r.n1, x.nb, 1e-6f, CS_ACT_SILU, vq_groups(r.cin), r.c1, nullptr, x.d, x.h, x.w);
-    // (want_stats: the conv's epilogue leaves the partial sums the next GroupNorm takes its statistics from -- vqvae.py::_res)
-    Buf h1 = gemm(h, r.c1, x.nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, 0, /*want_stats=*/true);
+    // (stats(): the conv's epilogue leaves the partial sums the next GroupNorm takes its statistics from -- vqvae.py::_res)
+    Buf h1 = gemm(h, r.c1, x.nb, x.d, x.h, x.w, GemmOpts().stats());
     release(h);
     Buf h2 = groupnorm(h1, r.n2, x.nb, 1e-6f, CS_ACT_SILU, vq_groups(r.cout), r.c2, nullptr, x.d, x.h, x.w);
     release(h1);
     Buf skip = x.b;
     if (r.nin >= 0) skip = gemm(x.b, r.nin, x.nb, x.d, x.h, x.w);
     Act o = x;
-    o.b = gemm(h2, r.c2, x.nb, x.d, x.h, x.w, 1, 0, CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(skip), skip.c, 0, 1, 0,
-               /*want_stats=*/true);
+    o.b = gemm(h2, r.c2, x.nb, x.d, x.h, x.w, GemmOpts().residual(skip, skip.c).stats());
     release(h2);
     if (r.nin >= 0) release(skip);
     return o;
@@ -147,7 +146,7 @@ struct VExec : ExecBase {
     Buf qkv = linear(hn, u.g_qkv);
     release(hn);
     Buf a = alloc(rows, c);
-    // r6: static operand scales of q / k / v and of the attention output (vqvae.py::_attn: the same rule, the same statistics)
+    // static operand scales of q / k / v and of the attention output (vqvae.py::_attn: the same rule, the same statistics)
     float ss[4];
     const float qks = (float)std::pow((double)c, -0.5);
     const bool stat = attnblock_scales(u.n_attn, (int64_t)n * (c / vq_groups(c)), c, u.attn_l2max, u.attn_bmax, qks, ss);
@@ -155,7 +154,7 @@ struct VExec : ExecBase {
     if (stat) a.a_scale = ss[3];
     release(qkv);
     Act o = x;
-    o.b = linear(a, u.g_proj, CS_ACT_NONE, nullptr, 0, 1, dry ? nullptr : p(x.b), c);
+    o.b = linear(a, u.g_proj, GemmOpts().residual(x.b, c));
     release(a);
     return o;
   }
@@ -185,7 +184,7 @@ int decode(VExec& e, const float* latent_ncdhw, float* sdf_ncdhw, int64_t* idx_o
   h.nb = nb; h.d = h.h = h.w = g;
   Buf q4 = e.gemm(zl, u.g_post, nb, g, g, g);              // post_quant_conv (1x1x1)
   e.release(zl);
-  h.b = e.gemm(q4, u.g_conv_in, nb, g, g, g, 1, 0, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, 0, /*want_stats=*/true);
+  h.b = e.gemm(q4, u.g_conv_in, nb, g, g, g, GemmOpts().stats());
   e.release(q4);
   auto step = [&](Act o) {
     e.release(h.b);
@@ -198,7 +197,7 @@ int decode(VExec& e, const float* latent_ncdhw, float* sdf_ncdhw, int64_t* idx_o
     for (const ResP& r : u.up[lvl]) step(e.res(r, h));
     if (u.up_conv[lvl] >= 0) {     // Upsample (vqvae_modules.py:35-39): nearest x2 in D, H, W as conv addressing
       Act o = h;
-      o.b = e.gemm(h.b, u.up_conv[lvl], h.nb, h.d, h.h, h.w, 1, 1, CS_ACT_NONE, nullptr, 0, 1, nullptr, 0, 0, 1, 1);
+      o.b = e.gemm(h.b, u.up_conv[lvl], h.nb, h.d, h.h, h.w, GemmOpts().upsample(1, 1));
       o.d = h.d * 2; o.h = h.h * 2; o.w = h.w * 2;
       step(o);
     }
@@ -241,7 +240,7 @@ extern "C" int64_t cs_vqvae_arena_bytes(const cs_vqvae* u) { return u ? u->arena
 extern "C" int cs_vqvae_pack(cs_vqvae* u, const void* raw_dev, void* arena_dev, cs_stream_t stream) {
   const int rc = pack_plan(u, raw_dev, arena_dev, stream);
   if (rc != CS_OK || !u || u->math != CS_MATH_F16X3 || u->extra_slots < 4) return rc;
-  // r6: the attention block's static-bound statistics (vqvae.py::_pack: the same kernel on the same tensors, the same values):
+  // the attention block's static-bound statistics (vqvae.py::_pack: the same kernel on the same tensors, the same values):
   // {max row 2-norm, max |.|} over the q, k, v weights into slots 0-1, over their biases into slots 2-3
   hipStream_t st = (hipStream_t)stream;
   const char* raw = reinterpret_cast<const char*>(raw_dev);
