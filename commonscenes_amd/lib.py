@@ -184,6 +184,9 @@ SIGNATURES = {
     "cs_scene_apply": (_i, [_f, _l, _f, _l, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _f, _f, _l, _f, _f, _l, _s]),
     "cs_scene_raster_topdown": (_i, [_f, _l, _f, _l, _i, _fl, _f, _f, _s]),
     "cs_scene_resolve": (_i, [_f, _f, _l, _f, _l, _f, _f, _i, _f, _f, _f, _s]),
+    "cs_scene_constraints": (_i, [_f, _l, _i, _i, _f, _l, _f, _f, _i, _f, _i, _f, _i, _f, C.c_double, _i, C.c_double, _f, _f, _f,
+                                  _s]),
+    "cs_box3d_iou_pairs": (_i, [_f, _f, _l, _i, _i, _i, _f, _f, _s]),
     "cs_chamfer_nm_distance": (_i, [_f, _f, _f, _f, _i, _i, _i, _s]),
     "cs_unet_create": (_i, [C.POINTER(CsUnetConfig), _pp]),
     "cs_unet_destroy": (None, [C.c_void_p]),
@@ -275,6 +278,7 @@ class CsSplitKTimeout(CsError):
 STATUS_F16X3_OVERFLOW = 1
 STATUS_INTERNAL = 2
 STATUS_SPLITK_TIMEOUT = 4
+STATUS_CONSTRAINT_RANGE = 8
 
 
 def check(rc: int, what: str) -> None:

@@ -61,6 +61,9 @@ typedef struct ihipStream_t* cs_stream_t; /* == hipStream_t */
  *   launch's output is incomplete and the counters may be left non-zero: zero splitk_sync and re-run with the two-kernel
  *   form (CsDebug.no_fused_reduce = 1 / splitk_sync = NULL) -- the host classes do. */
 #define CS_STATUS_SPLITK_TIMEOUT 4
+/*   CS_STATUS_CONSTRAINT_RANGE: cs_scene_constraints met a triple whose subject, object or predicate id (or whose scene's
+ *   CSR range) leaves its bounds; that triple got verdict -1 and nothing was dereferenced. */
+#define CS_STATUS_CONSTRAINT_RANGE 8
 
 /*
  * Debug / A-B switches (r4: ONE struct instead of ~40 getenv() calls spread over two host languages).  All zero = the
@@ -835,6 +838,44 @@ int cs_scene_raster_topdown(const float* verts, int64_t nverts, const int64_t* f
 int cs_scene_resolve(const uint64_t* keys, const float* verts, int64_t nverts, const int64_t* faces, int64_t nfaces,
                      const float* vert_rgb, const int32_t* face_object, int size, float* depth, int32_t* object_id,
                      uint8_t* rgb, cs_stream_t stream);
+
+/*
+ * Scene-graph constraint accuracy (csrc/cs_constraints.hip): the layout table of scripts/eval_3dfront.py:411-415,722, i.e.
+ * helpers/metrics_3dfront.py:57-179 validate_constrains and :182-311 validate_constrains_changes, which walk the triples on
+ * the host with two box read-backs each.  Every buffer is caller-owned device memory; nothing allocates or synchronises.
+ *
+ * cs_scene_constraints: all triples of a ragged batch of scenes in one launch, one thread per triple.
+ *   boxes [n_boxes][ld] fp32, params = 6 or 7 leading columns l, h, w, px, py, pz[, angle], packed over the scenes;
+ *   triples [n_triples][3] int64 (s, p, o), s and o LOCAL to their scene; box_ptr / triple_ptr [n_scenes + 1] int64: CSR
+ *   offsets of the scenes; pred_code [n_preds] int32: predicate index -> category 0..10 = left, right, front, behind, bigger,
+ *   smaller, taller, shorter, standing on, close by, symmetrical to (anything else, e.g. -1: not evaluated);
+ *   keep [n_boxes] uint8 (NULL allowed for mode 0) and mode: 0 every triple (:64-66), 1 only triples with keep == 1 on both
+ *   nodes (:68-72), 2 only triples with keep == 0 on either node (:192-196);
+ *   norm [2][7] fp64 = mean, std of helpers/util.py:536-559 denormalize_box_params, applied in fp64 as (box * std) / scale +
+ *   mean (:559), or NULL for with_norm=False; strict / overlap_threshold as :57-58.
+ *   -> verdict [n_triples] int8: -1 skipped (mode, pred_code or range), 0 violated, 1 satisfied;
+ *      counts [n_scenes][11][2] int32 = (satisfied, evaluated) per scene and category: zeroed by the call, then integer
+ *      atomics (exact, order-free);  status: sticky CS_STATUS_* word or NULL, CS_STATUS_CONSTRAINT_RANGE for a triple whose
+ *      s, o, p or scene range leaves its bounds (verdict -1, nothing dereferenced).
+ *   The rules are :74-177 in fp64 in the reference's operation order, no contraction, IEEE comparisons and divisions:
+ *   left / right compare pz and front / behind px with +-0.05 (:76-97) and, when strict, box3d_iou(...)[0] > threshold;
+ *   bigger / smaller (:104-117) and taller / shorter (:124-137) divide by the subject's value (0 -> inf / nan, as numpy);
+ *   standing on :146; close by :154-157 through close_dis's expanded form :10-15 (a negative argument gives nan, the minimum
+ *   hands it on, nan > 0.45 is false: satisfied); symmetrical to :166-172.
+ *   mode 2 with params = 7 -> CS_EINVAL: :201 calls box3d_iou with its 6-parameter default and cannot unpack seven values.
+ * cs_box3d_iou_pairs: box3d_iou(box1, box2, param6, with_translation) (:337-370) of m pairs of denormalised boxes
+ *   [m][ld] fp32 -> iou, iou_2d [m] fp64; the device function the constraint kernel calls.  The angle is ignored (:328
+ *   rotates by the identity), iou divides by the SMALLER volume (:366-368), the footprint intersection is the
+ *   Sutherland-Hodgman clip of :396-439 on the (z, x) rectangles in corners_from_box's order (:314-334) with its strict
+ *   inside test, and the clipped polygon's area is the shoelace sum where the reference asks scipy's ConvexHull (:380).
+ *   Where the reference raises (fewer than three vertices left) the area is 0 here.
+ */
+int cs_scene_constraints(const float* boxes, int64_t n_boxes, int ld, int params, const int64_t* triples, int64_t n_triples,
+                         const int64_t* box_ptr, const int64_t* triple_ptr, int n_scenes, const int32_t* pred_code,
+                         int n_preds, const uint8_t* keep, int mode, const double* norm, double scale, int strict,
+                         double overlap_threshold, int8_t* verdict, int32_t* counts, int32_t* status, cs_stream_t stream);
+int cs_box3d_iou_pairs(const float* box1, const float* box2, int64_t m, int ld, int params, int with_translation, double* iou,
+                       double* iou_2d, cs_stream_t stream);
 
 /*
  * Whole-forward driver (SURVEY 8b "cs_unet_step"): UNet3DModel.forward (openai_model_3d.py:752-789) with the

@@ -36,6 +36,12 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 VOCAB = dict(object_idx_to_name=[f"obj{i}\n" for i in range(35)], pred_idx_to_name=[f"pred{i}\n" for i in range(16)],
              object_idx_to_name_grained=[f"objg{i}\n" for i in range(35)])
+# --constraints: what the synthetic predicates stand for in the evaluation ONLY (the model keeps pred0..pred15): predicate 0 is
+# synth.random_scene_graph's `in` edge, 1..11 the eleven relations helpers/metrics_3dfront.py:74-165 evaluates, the rest are
+# relations it does not evaluate
+EVAL_PREDICATES = ["in", "left", "right", "front", "behind", "bigger than", "smaller than", "taller than", "shorter than",
+                   "standing on", "close by", "symmetrical to", "inside", "attached to", "part of", "cover"]
+EVAL_VOCAB = dict(pred_idx_to_name=[p + "\n" for p in EVAL_PREDICATES])
 
 
 def sample_points(points_list, num):                         # helpers/util.py:31-44
@@ -181,6 +187,9 @@ def main():
                          "hands to trimesh.Scene, helpers/visualize_scene.py:401-436) and render its 256x256 top-down view "
                          "(render_img, :85-116); writes DIR/<scan>.obj and DIR/<scan>.png (.npy without PIL) and reports the "
                          "device time next to a host numpy restatement of the fit (helpers/util.py:158-189)")
+    ap.add_argument("--constraints", action="store_true",
+                    help="additionally evaluate every scene's sampled boxes against its graph (constraints.validate_constrains: "
+                         "scripts/eval_3dfront.py:722 -> helpers/metrics_3dfront.py:57-179) and report the accuracy table")
     a = ap.parse_args()
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -273,6 +282,9 @@ def main():
                                        boxes_equal=all(bool(torch.equal(x[0][0], y[0][0])) for x, y in zip(o1, o2)),
                                        note="shape sampling + decode of all scenes: one sample_box_and_shape call per scene "
                                             "(eval_3dfront.py:484-513) vs VAE.sample_box_and_shape_many")
+        if a.constraints:
+            from commonscenes_amd import constraints as CN
+            accuracy, mapped = CN.new_accuracy(), 0
         x_T = None                                            # like the reference: fresh noise per call
         all_div_boxes, all_div_angles, all_div_chamfer = [], [], []
         t_all = time.perf_counter()
@@ -287,6 +299,9 @@ def main():
                                                                      ddim_steps=a.ddim_steps)
                 boxes_pred, angles_pred = boxes_pred
                 angles_pred = -180 + (torch.argmax(angles_pred, dim=1, keepdim=True) + 1) * 15.0
+            if a.constraints:                                                  # eval_3dfront.py:722
+                CN.validate_constrains(dec_triples, boxes_pred, None, None, EVAL_VOCAB, accuracy)
+                mapped += sum(1 for p in d["tripltes"][:, 1].tolist() if 1 <= p <= 11)
             meshes = sdf_to_mesh(shapes_pred, render_all=True)                 # --visualize (helpers/util.py:298)
             torch.cuda.synchronize()
             t_scene = time.perf_counter() - t0
@@ -326,6 +341,9 @@ def main():
         res.update(total_s=time.perf_counter() - t_all, box_std_mean=float(np.mean(all_div_boxes)),
                    angle_std_mean=float(np.mean(all_div_angles)), chamfer_diversity_mean=float(np.mean(all_div_chamfer)),
                    chamfer_diversity_n=len(all_div_chamfer))
+        if a.constraints:
+            res["accuracy"] = dict({k: dict(satisfied=int(sum(v)), evaluated=len(v)) for k, v in accuracy.items()},
+                                   mapped_triples=mapped)
     if rank == 0:
         print("EVAL_WALKTHROUGH " + json.dumps(res), flush=True)
     if world > 1:
