@@ -912,6 +912,11 @@ extern "C" int cs_groupnorm_parts(const float* x, const CsGnSeg* segs, int nseg,
     CS_CHECK_LAUNCH();
     return CS_OK;
   }
+  // what cs_groupnorm_apply (float4 accesses) will ask for, checked BEFORE the finalize launch: a call that is turned down
+  // has written nothing (c % 4 != 0 used to leave stats and bound behind and then return CS_EINVAL)
+  if ((c & 3) || (ldx & 3) || (ldy & 3) || nb > 65535 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) ||
+      ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15))
+    return CS_EINVAL;
   const int rc = cs_groupnorm_finalize_parts(segs, nseg, nb, rows, c, groups, eps, stats, bound, stream);
   if (rc) return rc;
   return cs_groupnorm_apply(x, stats, gamma, beta, y, nb, rows, c, ldx, ldy, groups, act, stream);

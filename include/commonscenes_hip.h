@@ -481,7 +481,9 @@ int cs_groupnorm_finalize_parts(const CsGnSeg* segs, int nseg, int nb, int rows,
                                 float* stats, float* bound, cs_stream_t stream);
 /* ... and the whole GroupNorm (+ activation) from them in one call, the counterpart of cs_groupnorm: ONE launch for small
  * tensors (the same size rule: one workgroup per (sample, group) adds the group's partials and makes a single sweep over
- * it), cs_groupnorm_finalize_parts + cs_groupnorm_apply otherwise.  `stats` is written either way. */
+ * it), cs_groupnorm_finalize_parts + cs_groupnorm_apply otherwise.  `stats` is written either way.  The one-launch kernel
+ * uses scalar accesses (any c); the two-launch form needs cs_groupnorm_apply's c % 4 == 0 and 16-byte alignment, checked
+ * before its first launch: a call that returns CS_EINVAL has written nothing. */
 int cs_groupnorm_parts(const float* x, const CsGnSeg* segs, int nseg, const float* gamma, const float* beta, float* y,
                        int nb, int rows, int c, int ldx, int ldy, int groups, float eps, int act, float* stats,
                        float* bound, cs_stream_t stream);
