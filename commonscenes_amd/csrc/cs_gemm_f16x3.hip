@@ -1555,6 +1555,10 @@ int cs_conv_gemm_f16x3_dispatch(const CsConvGemm& p_in, int M, int tile, int spl
       }
     }
 #endif
+    // the stacked Winograd-W positions (omap_f bit 4) exist on the three-tap slab kernel only -- it alone selects the position's
+    // weight image: a launch that kernel does not take (a slice count cs_f16x3_slab_width sends back to the per-tap gather,
+    // which would read image 0 for every position) is refused, not run
+    if (omap_f & 16) return CS_EINVAL;
     if (tile == 8) tile = 7;      // (only reachable in -DCS_NO_SLAB builds)
     if (tile == 9) tile = 6;
     switch (tile) {
