@@ -725,6 +725,23 @@ extern "C" int cs_conv_gemm_plan(const CsConvGemm* d, int32_t* splitk, int64_t* 
   return CS_OK;
 }
 
+// cs_conv_plan_copies: the calling thread's launches each serve this many identical copies of their batch (the guidance halves
+// of cs_unet_step share such launches).  The rules that follow the batch -- the automatic tile, the Winograd-W variant, its K
+// slices and tail cut -- are asked about the duplicated batch, so a sample keeps the summation order it has there
+static thread_local int tl_plan_copies = 1;
+extern "C" int cs_conv_plan_copies(int copies) {
+  if (copies < 1 || copies > 64) return CS_EINVAL;
+  const int prev = tl_plan_copies;
+  tl_plan_copies = copies;
+  return prev;
+}
+// the descriptor the batch-following rules look at
+static CsConvGemm planned(const CsConvGemm& p) {
+  CsConvGemm q = p;
+  if (tl_plan_copies > 1 && (int64_t)p.nb * tl_plan_copies <= 0x7fffffffLL) q.nb = p.nb * tl_plan_copies;
+  return q;
+}
+
 // most 64x64 tiles a launch may have and still take the K-wave kernel (one 128 KB workgroup per CU): four rounds of the chip
 // (r5, 7 objects: 24.09 / 24.05 ms per step at one round, 23.94 / 23.92 at four -- the level-2 C x C GEMMs of 616 tiles ran
 // at 73 TF/s on the one-chain tile, profiles/r05_e_kwave_tiles_ab.txt); CS_KWAVE_MAX_TILES overrides (tuning sweeps)
@@ -745,8 +762,11 @@ static int tok_t2_maxk() {
 }
 
 // tile of an automatic (desc->tile == 0) launch
-static int auto_tile(const CsConvGemm& p, int M, bool f16x3) {
+static int auto_tile(const CsConvGemm& p, int M_launch, bool f16x3) {
   int tile = 0;
+  // (cs_conv_plan_copies: the tile of the duplicated batch -- the K-wave tile partitions the K sum)
+  const int64_t M_all = (int64_t)M_launch * tl_plan_copies;
+  const int M = M_all > 0x7fffffffLL ? 0x7fffffff : (int)M_all;
   {
     // largest tile that still gives every one of the 256 CUs a workgroup; small problems take the 64x64 tile
     // (measured at CFG batch 2: 64x64 is ~2x the 128x224 tile, which leaves 3/4 of the chip idle)
@@ -908,7 +928,7 @@ static bool wino23_ok(const CsConvGemm& p) {
 // F(4,3) (a_format = 4): six positions over M / 4 rows -- 13.5 of 27 multiply-adds, 1.5x (not 2x) operand / result passes, ~2x
 // the direct form's rounding error (6e-7 - 8e-7 per conv, profiles/r05_z_wino43_numerics.txt): W % 4
 // == 0, whole 256-row tiles per position, from CsDebug.wino43_min_rows rows
-static int wino_variant(const CsConvGemm& p) {
+static int wino_variant_at(const CsConvGemm& p) {
   if (!wino23_ok(p)) return 0;
   const CsDebug* dbg = cs_debug();
   const int64_t M = (int64_t)p.nb * p.dout * p.hout * p.wout;
@@ -919,6 +939,15 @@ static int wino_variant(const CsConvGemm& p) {
   const int64_t rdec = p.cout % 224 ? (int64_t)p.din * p.hin * p.win : M;
   if (!dbg->no_wino43 && p.win % 4 == 0 && (M / 4) % 256 == 0 && (rdec / 4) % 256 == 0 && rdec >= min43) return 4;
   return 2;
+}
+// ... of this launch: the duplicated batch's (cs_conv_plan_copies) where the launch's own rows allow it
+static int wino_variant(const CsConvGemm& p) {
+  const int v = wino_variant_at(p);
+  if (!v || tl_plan_copies <= 1) return v;
+  const int vq = wino_variant_at(planned(p));
+  const int64_t M = (int64_t)p.nb * p.dout * p.hout * p.wout;
+  if (vq == 4 && v == 2) return (p.win % 4 == 0 && (M / 4) % 256 == 0 && !cs_debug()->no_wino43) ? 4 : 2;
+  return vq ? vq : v;
 }
 // positions / outputs per tile of a variant
 static inline int wino_pos(int variant) { return variant + 2; }
@@ -946,7 +975,9 @@ struct WinoPlan {
 };
 static int wino_splits(const CsConvGemm& p, int variant, double* cost_us = nullptr);
 
-static WinoPlan wino_plan(const CsConvGemm& p, int variant) {
+static WinoPlan wino_plan(const CsConvGemm& p_launch, int variant) {
+  // (cs_conv_plan_copies: slices and tail cut of the duplicated batch -- the cut is by unit, so it applies to any row count)
+  const CsConvGemm p = planned(p_launch);
   WinoPlan pl;
   double t_uni = 0;
   pl.slices = wino_splits(p, variant, &t_uni);

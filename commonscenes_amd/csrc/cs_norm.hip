@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "cs_common.h"
+#include "cs_ln_pair.h"
 
 namespace {
 
@@ -626,42 +627,7 @@ __global__ __launch_bounds__(256) void ln_pair_kernel(const float* __restrict__ 
       if (c4 < ch4) v[k] = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
       s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     }
-    const float mean = wave_sum(s) / (float)c;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      const int c4 = lane + 64 * k;
-      if (c4 < ch4) {
-        const float a = v[k].x - mean, b = v[k].y - mean, cc = v[k].z - mean, d = v[k].w - mean;
-        q += (a * a + b * b) + (cc * cc + d * d);
-      }
-    }
-    const float var = wave_sum(q) / (float)c;
-    const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      const int c4 = lane + 64 * k;
-      if (c4 < ch4) {
-        const float4 g = *reinterpret_cast<const float4*>(gamma + c4 * 4);
-        const float4 b = *reinterpret_cast<const float4*>(beta + c4 * 4);
-        // the fp32 LayerNorm's expression, then the operand scale (a power of two: exact)
-        const float o[4] = {((v[k].x - mean) * rstd * g.x + b.x) * a_scale, ((v[k].y - mean) * rstd * g.y + b.y) * a_scale,
-                            ((v[k].z - mean) * rstd * g.z + b.z) * a_scale, ((v[k].w - mean) * rstd * g.w + b.w) * a_scale};
-        h4v hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          amax = fmaxf(amax, fabsf(o[e]));
-          const _Float16 h = (_Float16)o[e];
-          hi[e] = h;
-          lo[e] = (_Float16)(o[e] - (float)h);
-        }
-        // channel 4*c4 + e sits in chunk (4*c4) / 16 at j = (4*c4) % 16: hi at halves (j < 8 ? 0 : 16) + j % 8, lo 8 further
-        const int cch = c4 >> 2, j = (c4 & 3) * 4;
-        _Float16* dst = y + row * (int64_t)ldy * 2 + cch * 32 + (j < 8 ? 0 : 16) + (j & 7);
-        *reinterpret_cast<h4v*>(dst) = hi;
-        *reinterpret_cast<h4v*>(dst + 8) = lo;
-      }
-    }
+    amax = cs_ln_pair_row<MAXV>(v, s, lane, ch4, c, gamma, beta, y + row * (int64_t)ldy * 2, eps, a_scale, amax);
   }
   if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
 }

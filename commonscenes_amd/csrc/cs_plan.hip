@@ -64,6 +64,7 @@ void parse_env(CsDebug& d) {
   d.no_wino43 = flag("CS_NO_WINO43");
   d.wino43_min_rows = (int32_t)num("CS_WINO43_MIN_ROWS", 2048);
   d.no_wino_tail = flag("CS_NO_WINO_TAIL");
+  d.no_cfg_late_split = flag("CS_NO_CFG_LATE_SPLIT");
 }
 
 }  // namespace

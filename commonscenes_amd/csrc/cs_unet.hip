@@ -410,17 +410,21 @@ struct Exec : ExecBase {
     return o;
   }
 
-  Act attn_block(const Layer& l, const Act& x, const float* ctxvec) {
+  // twin (forward: the late guidance split): x holds ONE copy per (x, t) pair and everything up to the attn1.to_out product
+  // runs on it; the cross-attention row vector -- the first term that differs between the guidance halves -- enters in
+  // cs_twin_layernorm_pair16, which writes t1 and norm3's operand pair for both halves; the rest runs at 2 x.nb samples
+  Act attn_block(const Layer& l, const Act& x, const float* ctxvec, bool twin = false) {
     const int c = l.cin, heads = u.cfg.num_heads, dh = c / heads;
     const int n = x.d * x.h * x.w;
-    const int64_t rows = (int64_t)x.nb * n;
+    const int nbo = twin ? 2 * x.nb : x.nb;
+    const int64_t rows = (int64_t)nbo * n;
     Buf xn = groupnorm(x.b, l.n[0], x.nb, 1e-6f, CS_ACT_NONE);
     Buf t0 = linear(xn, l.g[0]);
     release(xn);
     Buf n1 = layernorm(t0, l.n[1]);
     Buf qkv = linear(n1, l.g[1]);
     release(n1);
-    Buf a = alloc(rows, c);
+    Buf a = alloc(t0.rows, c);
     // static bounds of the operands born inside the block (unet.py::_static_scales; the ONE rule in cs_plan.hip)
     float ss[12];
     const Norm& gnn = pl.norms[l.n[0]];
@@ -430,10 +434,28 @@ struct Exec : ExecBase {
     if (stat) a.a_scale = ss[3];
     release(qkv);
     // one context token: attn2(x) == to_out(to_v(ctx)) for every query row -> a row vector in this epilogue
-    Buf t1 = linear(a, l.g[2], GemmOpts().row_vector(ctxvec ? ctxvec + l.ctx_off : nullptr, u.ctx_total, n).residual(t0, c));
-    release(a);
-    release(t0);
-    Buf n3 = layernorm(t1, l.n[3]);
+    const float* rv = ctxvec ? ctxvec + l.ctx_off : nullptr;
+    Buf t1, n3;
+    if (twin) {
+      Buf y = linear(a, l.g[2]);
+      cs_conv_plan_copies(1);      // (forward set 2: the launches up to here stand for both guidance halves)
+      release(a);
+      const Norm& nm = pl.norms[l.n[3]];
+      t1 = alloc(rows, c);
+      n3 = alloc(rows, c);
+      n3.pair = true;
+      n3.a_scale = norm_a_scale(nm.gmax, nm.bmax, c);
+      if (ok() && !dry)
+        chk(cs_twin_layernorm_pair16(p(y), rv, p(t0), wf(nm.g_off), wf(nm.b_off), p(t1), p(n3), (int)y.rows, c, c, u.ctx_total, n, c,
+                                     c, c, 1e-5f, n3.a_scale, status, st));
+      release(y);
+      release(t0);
+    } else {
+      t1 = linear(a, l.g[2], GemmOpts().row_vector(rv, u.ctx_total, n).residual(t0, c));
+      release(a);
+      release(t0);
+      n3 = layernorm(t1, l.n[3]);
+    }
     Buf gg;
     // gg's only reader is ff.net.2, t2's only reader proj_out: both producers write the operand pair where they can
     // (unet.py::_attn, out_pair=)
@@ -454,9 +476,18 @@ struct Exec : ExecBase {
     release(gg);
     release(t1);
     Act o = x;
-    // (x.nb samples of n tokens: what the epilogue's GroupNorm partial sums are tiled by -- unet.py::_attn, spatial=)
-    o.b = gemm(t2, l.g[7], x.nb, n, 1, 1, GemmOpts().residual(x.b, c).stats());
+    o.nb = nbo;
+    // proj_out's residual is the block's input: one copy per guidance half
+    Buf x2;
+    if (twin) {
+      x2 = alloc(rows, c);
+      for (int g = 0; g < 2 && ok() && !dry; ++g)
+        chk(cs_copy_rows(p(x.b), p(x2) + (int64_t)g * x.b.rows * c, x.b.rows, c, c, c, st));
+    }
+    // (nbo samples of n tokens: what the epilogue's GroupNorm partial sums are tiled by -- unet.py::_attn, spatial=)
+    o.b = gemm(t2, l.g[7], nbo, n, 1, 1, GemmOpts().residual(twin ? x2 : x.b, c).stats());
     release(t2);
+    release(x2);
     return o;
   }
 
@@ -482,9 +513,11 @@ struct Exec : ExecBase {
   }
 
   // runs the layers of one block; `keep_in` says whether the caller still needs the input buffer
+  // twin: h holds one copy per guidance pair and the block's last layer is the transformer block that splits (attn_block)
   Act run(const std::vector<Layer>& layers, Act h, const Buf& semb, const float* ctxvec, bool keep_in,
-          const Act* split_skip = nullptr) {
+          const Act* split_skip = nullptr, bool twin = false) {
     bool owned = !keep_in;
+    if (twin) cs_conv_plan_copies(2);      // shared launches take the duplicated batch's launch rules: the same bits
     for (const Layer& l : layers) {
       Act o;
       if (l.kind == RES && l.ks > 0 && split_skip && &l == &layers[0]) {
@@ -503,7 +536,7 @@ struct Exec : ExecBase {
           o = res_block(l, h, semb);
           break;
         case ATTN:
-          o = attn_block(l, h, ctxvec);
+          o = attn_block(l, h, ctxvec, twin && &l == &layers.back());
           break;
         case ATTNBLOCK:
           o = attnblock(l, h);
@@ -532,7 +565,18 @@ struct Exec : ExecBase {
       h = o;
       owned = true;
     }
+    if (twin) cs_conv_plan_copies(1);
     return h;
+  }
+
+  // may this block split the guidance halves INSIDE its transformer block (ResBlocks, then one transformer block on the
+  // one-token row-vector route whose norm3 writes the operand pair)?  unet.py::forward_ndhwc asks the same
+  bool late_split(const std::vector<Layer>& layers) const {
+    if (u.cfg.math != CS_MATH_F16X3 || cs_debug()->no_cfg_late_split || cs_debug()->no_pair16) return false;
+    if (layers.size() < 2 || layers.back().kind != ATTN || layers.back().cin % 16) return false;
+    for (size_t i = 0; i + 1 < layers.size(); ++i)
+      if (layers[i].kind != RES) return false;
+    return true;
   }
 
   Buf duplicate(const Buf& a) {   // torch.cat([a, a], dim=0); the copy gets its own copy of the producer's partials
@@ -590,11 +634,21 @@ int forward(Exec& e, const float* x_ncdhw, const int64_t* t, const float* ctxvec
   bool first = true;
   for (const auto& layers : u.inp) {
     bool keep = !first;           // the block input is the previous block's output, retained in `hs`
+    bool twin = false;
     if (shared && has_attn(layers)) {
-      split(!first);              // the duplicate is a fresh buffer this block may consume
-      keep = false;
+      twin = e.late_split(layers);
+      if (!twin) {
+        split(!first);            // the duplicate is a fresh buffer this block may consume
+        keep = false;
+      }
     }
-    h = e.run(layers, h, semb, ctxvec, keep);
+    h = e.run(layers, h, semb, ctxvec, keep, nullptr, twin);
+    if (twin) {                   // the block's output holds both halves; the later blocks want their emb rows too
+      Buf s2 = e.duplicate(semb);
+      e.release(semb);
+      semb = s2;
+      shared = false;
+    }
     hs.push_back(h);
     first = false;
     if (!e.ok()) return e.rc;

@@ -77,7 +77,8 @@ class CsDebug(C.Structure):
         "plan_pow2", "slice_tile2", "no_gn_parts", "no_pair_epilogue", "no_dyn_scale", "no_tok_rules", "no_fused_reduce",
         "no_gn_fold", "no_kwave", "no_static_scales", "no_wino", "wino_min_rows", "no_wino43", "wino43_min_rows",
         "no_wino_tail")] + [
-        ("split16_min_rows", C.c_int64), ("cfg_split_min_rows", C.c_int64), ("gn_small_group", C.c_int64)]
+        ("split16_min_rows", C.c_int64), ("cfg_split_min_rows", C.c_int64), ("gn_small_group", C.c_int64),
+        ("no_cfg_late_split", C.c_int32)]
 
 
 class CsUnetConfig(C.Structure):
@@ -108,6 +109,7 @@ SIGNATURES = {
     "cs_conv_gemm_epilogue_caps": (_i, [C.POINTER(CsConvGemm), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_conv_wino_ok": (_i, [C.POINTER(CsConvGemm)]),
     "cs_conv_wino_plan": (_i, [C.POINTER(CsConvGemm), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "cs_conv_plan_copies": (_i, [_i]),
     "cs_conv_wino_plan_info": (_i, [C.POINTER(CsConvGemm), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_conv_wino_positions": (_i, [C.POINTER(CsConvGemm), _s]),
     "cs_conv_wino_output": (_i, [C.POINTER(CsConvGemm), _s]),
@@ -146,6 +148,7 @@ SIGNATURES = {
     "cs_groupnorm_apply_wino16_range": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _f, _s]),
     "cs_groupnorm_apply_wino_range": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _i, _f, _s]),
     "cs_layernorm_pair16": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _fl, _fl, _f, _s]),
+    "cs_twin_layernorm_pair16": (_i, [_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _fl, _f, _s]),
     "cs_groupnorm_apply_range": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "cs_groupnorm_apply_split16_range": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _f, _s]),
     "cs_groupnorm": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _fl, _i, _f, _f, _s]),

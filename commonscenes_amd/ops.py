@@ -1154,6 +1154,48 @@ def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5, out: Op
     return out
 
 
+def twin_layernorm(y: Tensor, rowvec: Tensor, rv_rows: int, res: Tensor, gamma: Tensor, beta: Tensor, pair_scale: float,
+                   eps: float = 1e-5) -> Tuple[Tensor, "Pair16"]:
+    """cs_twin_layernorm_pair16: the LayerNorm hand-over two guidance halves share.  y, res: [nb, n, c] common to both
+    halves; rowvec: the 2 nb halves' row vectors (one per rv_rows rows).  Returns t1 [2 nb, n, c] = (y + rowvec) + res per
+    half -- the add order of conv_gemm's epilogue -- and layernorm(t1, pair_scale=...) as a Pair16, bit for bit what the
+    GEMM epilogue and `layernorm` give on the duplicated batch; y and res are read once."""
+    _chk(y, "y")
+    _chk(res, "res")
+    _chk(rowvec, "rowvec")
+    m, c, ldy = rows_ld(y, "y")
+    rm, rc, ldr = rows_ld(res, "res")
+    vm, vc, ldrv = rows_ld(rowvec, "rowvec")
+    if (rm, rc) != (m, c) or vc != c or vm * rv_rows < 2 * m or c % 16:
+        raise L.CsError("twin_layernorm: shape mismatch")
+    shape = (2 * y.shape[0], *y.shape[1:])
+    t1 = torch.empty(shape, dtype=torch.float32, device=y.device)
+    pair = torch.empty(shape, dtype=torch.float32, device=y.device)
+    L.check(L.load().cs_twin_layernorm_pair16(y.data_ptr(), rowvec.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                              t1.data_ptr(), pair.data_ptr(), m, c, ldy, ldrv, int(rv_rows), ldr, c, c, eps,
+                                              float(pair_scale), status_word(y.device).data_ptr(), _stream()),
+            "cs_twin_layernorm_pair16")
+    return t1, Pair16(pair, float(pair_scale))
+
+
+class plan_copies:
+    """`with ops.plan_copies(2): ...` -- cs_conv_plan_copies: the launches inside serve that many identical copies of their
+    batch and take the duplicated batch's launch rules (tile, Winograd-W variant and K slices), hence its bits."""
+
+    def __init__(self, copies: int):
+        self.copies = int(copies)
+
+    def __enter__(self):
+        self.prev = L.load().cs_conv_plan_copies(self.copies)
+        if self.prev < 1:
+            raise L.CsError("cs_conv_plan_copies failed: invalid argument")
+        return self
+
+    def __exit__(self, *exc):
+        L.load().cs_conv_plan_copies(self.prev)
+        return False
+
+
 def bound_a_scale(bound: float) -> float:
     """cs_bound_a_scale: the largest power of two s with bound * s <= 65000 -- the F16X3 operand scale of a tensor whose
     magnitude is bounded by `bound` (ONE rule for every host)."""

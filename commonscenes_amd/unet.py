@@ -674,7 +674,18 @@ class DiffusionUNet:
                          spatial=(nb, n, 1, 1), a_scale=ss[3] if ss is not None else None)
         return ops.attach_stats(out.view(nb, d, h, w, c), getattr(out, "cs_stats", None))
 
-    def _attn(self, p: str, l: dict, x: Tensor, ctx, out_fn=None) -> Tensor:
+    def _late_split(self, layers, ctx) -> bool:
+        """May this block split the guidance halves INSIDE its transformer block (cs_unet.hip::late_split: the same rule)?
+        ResBlocks, then one transformer block on the one-token row-vector route whose norm3 writes the operand pair."""
+        return (self.math == L.MATH_F16X3 and not L.debug().no_cfg_late_split and ops._sw("PAIR16_PRODUCERS")
+                and isinstance(ctx, tuple) and self.cfg["use_spatial_transformer"] and len(layers) >= 2
+                and layers[-1]["kind"] == "attn" and layers[-1]["cin"] % 16 == 0
+                and all(l["kind"] == "res" for l in layers[:-1]))
+
+    def _attn(self, p: str, l: dict, x: Tensor, ctx, out_fn=None, twin: bool = False) -> Tensor:
+        """twin (the late guidance split, forward_ndhwc): x holds ONE copy per (x, t) pair and everything up to the
+        attn1.to_out product runs on it; attn2's row vector -- the first term that differs between the guidance halves --
+        enters in ops.twin_layernorm, which writes t1 and norm3's operand pair for both halves; the rest runs at 2 nb."""
         sd, pk = self._sd, self._packed
         heads = self.cfg["num_heads"]
         nb, d, h, w, c = x.shape
@@ -692,7 +703,14 @@ class DiffusionUNet:
         amath = self.attn_math if self.attn_math is not None else self.math
         a = ops.attention(qkv[..., 0:c], qkv[..., c:2 * c], qkv[..., 2 * c:3 * c], heads, dh ** -0.5, math=amath,
                           scales=ss["attn"] if (ss is not None and amath == L.MATH_F16X3) else None)
-        if isinstance(ctx, tuple):
+        s3 = self._nas(t + ".norm3", c)
+        n3 = None
+        if twin:
+            y = ops.linear(a, pk[t + ".attn1.to_out.0"], math=self.math, a_scale=ss["a"] if ss is not None else None)
+            L.load().cs_conv_plan_copies(1)     # (_run set 2: the launches up to here stand for both guidance halves)
+            t1, n3 = ops.twin_layernorm(y, ctx[1][t], n, t0, sd[t + ".norm3.weight"], sd[t + ".norm3.bias"], s3)
+            nb *= 2
+        elif isinstance(ctx, tuple):
             # one context token: softmax over one key == 1, attn2(x) = to_out(to_v(ctx)) for every
             # query row -> a per-sample row vector folded into the attn1 output GEMM.
             t1 = ops.linear(a, pk[t + ".attn1.to_out.0"], res=t0, rowvec=ctx[1][t], rv_rows=n, math=self.math,
@@ -705,8 +723,8 @@ class DiffusionUNet:
             vv2 = ops.linear(ctx, pk[t + ".attn2.to_v"], math=self.math)
             a2 = ops.attention(q2, k2, vv2, heads, dh ** -0.5, math=self.attn_math if self.attn_math is not None else self.math)
             t1 = ops.linear(a2, pk[t + ".attn2.to_out.0"], res=t1a, math=self.math)
-        s3 = self._nas(t + ".norm3", c)
-        n3 = ops.layernorm(t1, sd[t + ".norm3.weight"], sd[t + ".norm3.bias"], pair_scale=s3)
+        if n3 is None:
+            n3 = ops.layernorm(t1, sd[t + ".norm3.weight"], sd[t + ".norm3.bias"], pair_scale=s3)
         # r4: gg's only reader is ff.net.2 and t2's only reader is proj_out (attention.py:241-245, 349), so both producers
         # write the interleaved F16X3 operand pair where their launch can (out_pair: scale 16, the raw-activation default;
         # a value beyond the fp16 range is now flagged by the producer) -- the consumers' K loops carry no conversion.
@@ -723,13 +741,27 @@ class DiffusionUNet:
         t2 = ops.linear(gg, pk[t + ".ff.net.2"], res=t1, math=self.math, out_pair=pair_t2,
                         a_scale=None if isinstance(gg, ops.Pair16) or ss is None else ss["gg"])
         dst = out_fn((nb, d, h, w, c)).view(nb, n, c) if out_fn is not None else None
-        out = ops.linear(t2, pk[p + ".proj_out"], res=x.view(nb, n, c), math=self.math, out=dst, stats=True,
+        xr = x.view(x.shape[0], n, c)
+        if twin:      # proj_out's residual is the block's input: one copy per guidance half
+            xr = torch.empty((nb, n, c), dtype=torch.float32, device=x.device)
+            for g in range(2):
+                ops.copy_rows(x.view(nb // 2, n, c), xr[g * (nb // 2):(g + 1) * (nb // 2)])
+        out = ops.linear(t2, pk[p + ".proj_out"], res=xr, math=self.math, out=dst, stats=True,
                          spatial=(nb, n, 1, 1), a_scale=None if isinstance(t2, ops.Pair16) or ss is None else ss["t2"])
         return ops.attach_stats(out.view(nb, d, h, w, c), getattr(out, "cs_stats", None))
 
-    def _run(self, bp: str, layers, h: Tensor, semb: Tensor, ctx: Tensor, out_fn=None, split_skip=None) -> Tensor:
+    def _run(self, bp: str, layers, h: Tensor, semb: Tensor, ctx: Tensor, out_fn=None, split_skip=None,
+             twin: bool = False) -> Tensor:
         """`out_fn(shape) -> tensor`: where the block's LAST layer writes its result (a channel slice of the
-        concatenation buffer of the output block that consumes it: torch.cat([h, hs.pop()], 1) then costs no copy)."""
+        concatenation buffer of the output block that consumes it: torch.cat([h, hs.pop()], 1) then costs no copy).
+        twin: h holds one copy per guidance pair and the block's last layer is the transformer block that splits (_attn);
+        the shared launches take the duplicated batch's launch rules (ops.plan_copies), hence its bits."""
+        if twin:
+            with ops.plan_copies(2):
+                return self._run_layers(bp, layers, h, semb, ctx, out_fn, split_skip, True)
+        return self._run_layers(bp, layers, h, semb, ctx, out_fn, split_skip, False)
+
+    def _run_layers(self, bp: str, layers, h: Tensor, semb: Tensor, ctx: Tensor, out_fn, split_skip, twin: bool) -> Tensor:
         pk = self._packed
         for li, l in enumerate(layers):
             p = f"{bp}.{l['idx']}"
@@ -744,8 +776,8 @@ class DiffusionUNet:
                 else:
                     h = self._res(p, l, h, semb, of)
             elif k == "attn":
-                h = (self._attn(p, l, h, ctx, of) if self.cfg["use_spatial_transformer"]
-                     else self._attnblock(p, l, h, of))
+                h = (self._attn(p, l, h, ctx, of, twin=twin and li == len(layers) - 1)
+                     if self.cfg["use_spatial_transformer"] else self._attnblock(p, l, h, of))
             elif k == "down":      # dims == 3: inner two dims only (openai_model_3d.py:188); dims == 4: all three
                 # (Down / Upsample read the RAW stream with no GroupNorm in front: its bound from the producers' partials)
                 h = ops.conv_gemm(h, pk[p + ".op"], stride=(1, 2, 2) if self.cfg["dims"] == 3 else (2, 2, 2),
@@ -763,7 +795,10 @@ class DiffusionUNet:
         (samplers/ddim.py:206-209 builds x_in = cat([x] * 2)).  Everything upstream of the first
         cross-attention depends on (x, t) only, so `h`, `t` are passed once (B samples), ctx holds the 2B
         contexts [uc; c], the prefix blocks run at batch B and their outputs are shared by both halves.
-        Per-sample results are bit-identical to running the duplicated batch (rows never mix)."""
+        In F16X3 math with a one-token context the prefix reaches INTO the first attention block: its ResBlock and its
+        transformer block up to the attn1.to_out product run at batch B too, and the halves part where attn2's row
+        vector is added (ops.twin_layernorm; CS_NO_CFG_LATE_SPLIT=1: at the block's entry, the same bits).
+        Per-sample results are those of the duplicated batch (rows never mix; shared launches keep its launch rules)."""
         if self._packed is None:
             self._pack()
         sd, pk, P = self._sd, self._packed, self.prefix
@@ -808,14 +843,22 @@ class DiffusionUNet:
 
         shared = cfg_pairs          # True while h still holds one copy per (x, t) pair
         for i, layers in enumerate(inp):
+            twin = False
             if shared and any(l["kind"] == "attn" for l in layers):
-                st = getattr(h, "cs_stats", None)
-                h = torch.cat([h, h], dim=0)          # first context-dependent block: split into [uc; c]
-                ops.attach_stats(h, st)               # (sample n reads the partials of sample n % B)
-                semb = torch.cat([semb, semb], dim=0)
+                # first context-dependent block: split into [uc; c] -- inside its transformer block, at the cross-attention
+                # row vector (_attn, twin=), where the block allows it; else at its entry
+                twin = self._late_split(layers, ctx)
+                if not twin:
+                    st = getattr(h, "cs_stats", None)
+                    h = torch.cat([h, h], dim=0)
+                    ops.attach_stats(h, st)           # (sample n reads the partials of sample n % B)
+                    semb = torch.cat([semb, semb], dim=0)
                 shared = False
             direct = nocopy and not shared            # a skip at the full batch goes straight into its slice
-            h = self._run(f"{P}input_blocks.{i}", layers, h, semb, ctx, slot(nout - 1 - i, False) if direct else None)
+            h = self._run(f"{P}input_blocks.{i}", layers, h, semb, ctx, slot(nout - 1 - i, False) if direct else None,
+                          twin=twin)
+            if twin:                                  # the block's output holds both halves; so must the emb rows from here on
+                semb = torch.cat([semb, semb], dim=0)
             hs.append(None if direct else h)
             seg_r[nout - 1 - i] = getattr(h, "cs_stats", None)
             if tr is not None:
@@ -862,7 +905,8 @@ class DiffusionUNet:
     @torch.no_grad()
     def forward_cfg(self, x: Tensor, t: Tensor, c_in: Tensor) -> Tensor:
         """eps for the classifier-free-guidance pair batch without duplicating (x, t):
-        x (B,C,D,H,W), t (B,), c_in (2B,1,ctx) = [uc; c]  ->  (2B,C,D,H,W) = [eps_uc; eps_c]."""
+        x (B,C,D,H,W), t (B,), c_in (2B,1,ctx) = [uc; c]  ->  (2B,C,D,H,W) = [eps_uc; eps_c].
+        Everything up to the first use of the context runs once, at batch B (forward_ndhwc, cfg_pairs=True)."""
         if self.conditioning_key == "concat":
             # the condition is an input channel: nothing upstream of it to share, run the duplicated batch
             return self.forward(torch.cat([x, x]), torch.cat([t, t]), c_concat=[c_in])

@@ -142,7 +142,8 @@ class NativeDiffusionUNet:
 
     # ---- forward --------------------------------------------------------------------------------------------
     def _workspace(self, nb_x: int, cfg_pairs: bool) -> Tensor:
-        key = (nb_x, cfg_pairs)
+        # (the late guidance split changes the allocation pattern: a flipped switch must not meet a cached size)
+        key = (nb_x, cfg_pairs, int(L.debug().no_cfg_late_split))
         if self._ws_key != key:
             need = int(L.load().cs_unet_workspace_bytes(self._h, nb_x, 1 if cfg_pairs else 0))
             if need < 0:

@@ -110,6 +110,7 @@ typedef struct CsDebug {
   int64_t split16_min_rows;   /* pre-split operands on the 128-row slab tile from this many rows (8192; 0 = never) */
   int64_t cfg_split_min_rows; /* channel-split ResBlocks from this many rows (65536) */
   int64_t gn_small_group;     /* single-launch GroupNorm up to this many elements per (sample, group) (11264) */
+  int32_t no_cfg_late_split;  /* cfg_pairs: duplicate in front of the first context-dependent block, not inside it; same bits */
 } CsDebug;
 const CsDebug* cs_debug(void);
 void cs_debug_set(const CsDebug* d);
@@ -313,6 +314,14 @@ int cs_conv_gemm_plan(const CsConvGemm* desc, int32_t* splitk, int64_t* splitk_w
  * reads the variant from desc->a_format (3 or 4).) */
 int cs_conv_wino_ok(const CsConvGemm* desc);
 int cs_conv_wino_plan(const CsConvGemm* desc, int32_t* splitk, int64_t* ws_bytes);
+/* One launch that serves `copies` identical copies of its batch (cs_unet_step with cfg_pairs: the guidance halves share the
+ * context-free part of the first context-dependent block).  Some launch rules follow the batch and with it the fp32
+ * summation order: the automatic tile (the K-wave tile partitions the K sum; the tile's rows are the GroupNorm partial-sum
+ * tiles), the Winograd-W variant, its K slices and tail cut.  From this call on the calling thread's rule queries and launches
+ * evaluate them at copies x desc->nb samples, so each sample gets the bits it has in the duplicated batch (where the launch's
+ * own rows cannot run that batch's Winograd-W variant it keeps its own).  copies = 1 restores.  Returns the previous value;
+ * CS_EINVAL for copies outside [1, 64].  Host-only, no device work. */
+int cs_conv_plan_copies(int copies);
 /* (ABI 18) the shape of the position launch(es) behind that plan: `slices` = cs_conv_wino_plan's splitk; units_main > 0 = the
  * TAIL plan -- of the `units` (position, 224-column tile) units the first units_main run unsliced (whole rounds of the chip),
  * the rest as a second launch cut into `slices` K slices; units_main = 0 = every tile in `slices` uniform slices.  A unit's
@@ -503,6 +512,17 @@ int cs_layernorm(const float* x, const float* gamma, const float* beta, float* y
  * 64-byte pieces as from an fp32 tensor and its K loop carries no fp32 -> hi/lo conversion.  c, ldy % 16 == 0. */
 int cs_layernorm_pair16(const float* x, const float* gamma, const float* beta, void* y, int m, int c, int ldx, int ldy,
                         float eps, float a_scale, int32_t* status, cs_stream_t stream);
+
+/* The same LayerNorm behind an add that two guidance halves share (cs_unet_step with cfg_pairs, the first context-dependent
+ * transformer block): y [m][ldy] (a GEMM's plain output) and res [m][ldr] are common to both halves, rowvec
+ * [2 m / rv_rows][ldrv] holds the halves' row vectors.  For g in {0, 1} and r < m
+ *     t1[g m + r] = (y[r] + rowvec[(g m + r) / rv_rows]) + res[r]          fp32 [2 m][ldt]
+ *     pair[g m + r] = cs_layernorm_pair16's output for that row            the bytes of fp32 [2 m][ldp]
+ * -- the add order of cs_conv_gemm's epilogue (rowvec, then res), so t1 and pair carry the bits that GEMM and
+ * cs_layernorm_pair16 give on the duplicated batch; y and res are read once.  c, ldp % 16 == 0; the other strides % 4. */
+int cs_twin_layernorm_pair16(const float* y, const float* rowvec, const float* res, const float* gamma, const float* beta,
+                             float* t1, void* pair, int m, int c, int ldy, int ldrv, int rv_rows, int ldr, int ldt, int ldp,
+                             float eps, float a_scale, int32_t* status, cs_stream_t stream);
 
 /*
  * Multi-head attention, flash style (no score matrix in HBM), fp32.
@@ -899,7 +919,11 @@ int cs_box3d_iou_pairs(const float* box1, const float* box2, int64_t m, int ld, 
  *   cs_unet_step          eps = UNet(x, t, ctx).  x: NCDHW [nb_x][in_channels][d][h][w]; t: int64 [nb_x];
  *                         cfg_pairs = 0: nb_ctx == nb_x.  cfg_pairs = 1 (classifier-free guidance, ddim.py:206-209):
  *                         the SAME (x, t) under two contexts, ctxvec holds 2*nb_x rows [uc; c], the context-free
- *                         prefix runs once, eps is [2*nb_x] = [eps_uc; eps_c].  workspace >= cs_unet_workspace_bytes.
+ *                         prefix runs once, eps is [2*nb_x] = [eps_uc; eps_c].  The prefix ends at the first operation
+ *                         that reads the context: in F16X3 math that is the cross-attention row vector inside the first
+ *                         transformer block, whose ResBlock and self-attention still run at nb_x
+ *                         (cs_twin_layernorm_pair16 hands over; CsDebug.no_cfg_late_split: at that block's entry, as
+ *                         in fp32 math).  workspace >= cs_unet_workspace_bytes.
  * All return CS_OK / CS_EINVAL / CS_ENOMEM (workspace too small) / a hipError_t.
  */
 typedef struct CsUnetConfig {
