@@ -19,6 +19,28 @@ struct CsFuseK {
   float out_scale;
 };
 
+// Geometry terms of the host rules in cs_gemm.hip / cs_gemm_f16x3.hip.  Each rule there is its OWN conjunction of these (the
+// rules differ on purpose: W <= 32 or <= 64, with or without the pads or the extent check).
+inline bool cs_k333(const CsConvGemm& p) { return p.kd == 3 && p.kh == 3 && p.kw == 3; }
+inline bool cs_stride1(const CsConvGemm& p) { return p.sd == 1 && p.sh == 1 && p.sw == 1; }
+inline bool cs_no_upsample(const CsConvGemm& p) { return !(p.ud | p.uh | p.uw); }
+inline bool cs_conv333_s1(const CsConvGemm& p) { return cs_k333(p) && cs_stride1(p) && cs_no_upsample(p); }
+inline bool cs_pads1(const CsConvGemm& p) { return p.pd == 1 && p.ph == 1 && p.pw == 1; }
+inline bool cs_same_extent(const CsConvGemm& p) { return p.din == p.dout && p.hin == p.hout && p.win == p.wout; }
+// 32-bit byte offsets inside a workgroup's slab window: `rows` tile rows + two planes, two lines and a voxel row of halo, W = w
+inline bool cs_slab_window_ok(const CsConvGemm& p, int rows, int w) {
+  return (rows + 2LL * p.hin * w + 2 * w + 32) * p.lda * 4 < 0x7FF00000LL;
+}
+// K slices of the slab kernels are whole super-chunks (one kd x 16 channels): a slice count is taken only where that
+// granularity pads the slices by at most a tenth (42 super-chunks over 32 slices would leave a third of the workgroups idle)
+inline bool cs_slices_pad_ok(int64_t nsc, int64_t slices) { return ((nsc + slices - 1) / slices) * slices * 10 <= nsc * 11; }
+// the float4 epilogue needs whole float4 rows, 16-byte aligned, in every operand it touches
+inline bool cs_epilogue_vec4(const CsConvGemm& p) {
+  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+  return (p.cout % 4 == 0) && (p.ldo % 4 == 0) && al16(p.out) && (!p.bias || al16(p.bias)) &&
+         (!p.scale || (al16(p.scale) && al16(p.shift))) && (!p.rowvec || (p.ldrv % 4 == 0 && al16(p.rowvec))) &&
+         (!p.res || (p.ldr % 4 == 0 && al16(p.res)));
+}
 
 namespace cs16 {
 

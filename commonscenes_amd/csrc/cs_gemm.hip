@@ -280,8 +280,7 @@ bool split4_large(const CsConvGemm& p, int64_t M) {
 #ifdef CS_SPLIT4_FP32_ONLY
   if (p.a_format != 0) return false;
 #endif
-  return p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 && p.sw == 1 && !(p.ud | p.uh | p.uw) &&
-         ((p.cout / 224) & 1) && p.cout / 224 >= 3 && (p.cin + 15) / 16 >= 16 &&
+  return cs_conv333_s1(p) && ((p.cout / 224) & 1) && p.cout / 224 >= 3 && (p.cin + 15) / 16 >= 16 &&
          ((M + 255) / 256) * (int64_t)(p.cout / 224) >= 192;
 }
 
@@ -339,11 +338,11 @@ int plan_splitk(const CsConvGemm& p, int64_t M) {
   if (s < 1) s = 1;
   {
     // the slab kernel cuts K in whole super-chunks (nine taps) and is taken only where that pads the slices by at most a
-    // tenth (cs_conv_gemm_f16x3_dispatch: slab_slices_ok): the fewest slices of the same length (no empty last slice:
-    // 84 super-chunks over 15 slices of 6 is 14 slices), stepping down to the next count that qualifies
+    // tenth (cs_slices_pad_ok): the fewest slices of the same length (no empty last slice: 84 super-chunks over 15 slices
+    // of 6 is 14 slices), stepping down to the next count that qualifies
     const int64_t nsc = 3LL * ((p.cin + 15) / 16);
     s = (nsc + (nsc + s - 1) / s - 1) / ((nsc + s - 1) / s);
-    while (s > 1 && ((nsc + s - 1) / s) * s * 10 > nsc * 11) {
+    while (s > 1 && !cs_slices_pad_ok(nsc, s)) {
       --s;
       s = (nsc + (nsc + s - 1) / s - 1) / ((nsc + s - 1) / s);
     }
@@ -653,12 +652,8 @@ extern "C" int cs_conv_gemm_epilogue_caps(const CsConvGemm* d, int32_t* gn_rows,
   const int64_t M64 = (int64_t)p.nb * p.dout * p.hout * p.wout;
   if (M64 > 0x7fffffffLL) return CS_OK;
   const int M = (int)M64;
-  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   const int ocols = p.act == CS_ACT_GEGLU ? p.cout / 2 : p.cout;
-  const bool vec = (p.cout % 4 == 0) && (p.ldo % 4 == 0) && al16(p.out) && (!p.bias || al16(p.bias)) &&
-                   (!p.scale || (al16(p.scale) && al16(p.shift))) && (!p.rowvec || (p.ldrv % 4 == 0 && al16(p.rowvec))) &&
-                   (!p.res || (p.ldr % 4 == 0 && al16(p.res)));
-  if (!vec) return CS_OK;
+  if (!cs_epilogue_vec4(p)) return CS_OK;
   const bool pair_geom = (ocols % 8 == 0) && (p.ldo % 16 == 0) && (((uintptr_t)p.out & 63) == 0);
   int64_t rps = (int64_t)p.dout * p.hout * p.wout;           // output rows per sample
   int bm = 0, bn = 0;
@@ -795,8 +790,7 @@ static int auto_tile(const CsConvGemm& p, int M_launch, bool f16x3) {
     // 366-377 / 434-451 for the 256-row tiles, profiles/r03_g_decode_tables.txt.  CS_TILE512=1 selects them for A/B runs.)
     {
       const bool t512on = cs_debug()->tile512 != 0;
-      const bool conv3 = p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 && p.sw == 1 &&
-                         !(p.ud | p.uh | p.uw) && p.pd == 1 && p.ph == 1 && p.pw == 1;
+      const bool conv3 = cs_conv333_s1(p) && cs_pads1(p);
       const int64_t t512 = (M + 511) / 512;
       if (t512on && conv3 && tile == 7 && p.cout == 64 && p.win <= 64 && t512 >= 512) tile = 8;
       if (t512on && conv3 && tile == 6 && p.win <= 32 && t512 * (p.cout / 128) >= 512) tile = 9;
@@ -851,9 +845,7 @@ static int auto_tile(const CsConvGemm& p, int M_launch, bool f16x3) {
 // four-way cut, an explicit tile 4 and -- r3 -- every 3x3x3 slab conv (CS_SLICE_TILE2=1: those on the 128-row tile); else 128x224
 static int sliced_tile(const CsConvGemm& p, int M) {
   if (p.tile == 6 || p.tile == 7) return p.tile;
-  const bool slab3 = !cs_debug()->slice_tile2 && p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 &&
-                     p.sw == 1 && p.pd == 1 && p.ph == 1 && p.pw == 1 && !(p.ud | p.uh | p.uw) && p.din == p.dout &&
-                     p.hin == p.hout && p.win == p.wout && p.win <= 32;
+  const bool slab3 = !cs_debug()->slice_tile2 && cs_conv333_s1(p) && cs_pads1(p) && cs_same_extent(p) && p.win <= 32;
   return (split4_large(p, M) || p.tile == 4 || slab3) ? 4 : 2;
 }
 
@@ -909,9 +901,7 @@ static bool wino_ok(const CsConvGemm& p) { return wino_variant(p) != 0; }
 static bool wino23_ok(const CsConvGemm& p) {
   const CsDebug* dbg = cs_debug();
   if (dbg->no_wino || p.math != CS_MATH_F16X3 || p.act == CS_ACT_GEGLU) return false;
-  if (!(p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 && p.sw == 1 && p.pd == 1 && p.ph == 1 && p.pw == 1) ||
-      (p.ud | p.uh | p.uw) || p.din != p.dout || p.hin != p.hout || p.win != p.wout)
-    return false;
+  if (!(cs_conv333_s1(p) && cs_pads1(p) && cs_same_extent(p))) return false;
   if ((p.win & 1) || p.win < 4 || p.win / 2 > 32 || !wino_tile(p.cout) || (p.cin & 7) || p.cin < 16) return false;
   // The VQ decoder's widths (64 / 128 / 256 columns) only at its 16^3 level: at 32^3 and 64^3 the transformed operand, the
   // position results and the output transform are passes over 1 - 8 GB per conv that cost more than a third of a K loop of
@@ -922,7 +912,7 @@ static bool wino23_ok(const CsConvGemm& p) {
   const int64_t min_rows = dbg->wino_min_rows > 0 ? dbg->wino_min_rows : 1024;
   if (M < min_rows || M > 0x3fffffffLL || (M / 2) % 256) return false;
   // (32-bit offsets of the position GEMMs' slab windows and of the reduce kernel's workspace reads)
-  if ((512 + 2LL * p.hin * (p.win / 2) + p.win + 32) * p.lda * 4 >= 0x7FF00000LL) return false;
+  if (!cs_slab_window_ok(p, 512, p.win / 2)) return false;          // (W is even here)
   return true;
 }
 // F(4,3) (a_format = 4): six positions over M / 4 rows -- 13.5 of 27 multiply-adds, 1.5x (not 2x) operand / result passes, ~2x
@@ -1090,9 +1080,7 @@ static int conv_wino(const CsConvGemm& p, int M, hipStream_t s, int phases = 3) 
   if (!v || !p.x_lo || !al16(p.x_lo) || !p.w_lo || !al16(p.w_lo) || (p.lda & 7) || !p.splitk_ws || !al16(p.splitk_ws) ||
       p.a_bound || !(p.acc_scale > 0.f))
     return CS_EINVAL;
-  if ((p.ldo & 3) || !al16(p.out) || (p.bias && !al16(p.bias)) || (p.scale && (!al16(p.scale) || !al16(p.shift))) ||
-      (p.rowvec && ((p.ldrv & 3) || !al16(p.rowvec))) || (p.res && ((p.ldr & 3) || !al16(p.res))))
-    return CS_EINVAL;
+  if (!cs_epilogue_vec4(p)) return CS_EINVAL;          // (cout % 4 == 0: wino_tile)
   const int sp = p.splitk > 1 ? p.splitk : 1;
   if (sp > 16) return CS_EINVAL;
   CsConvGemm q = p;
@@ -1190,9 +1178,7 @@ static int conv_gemm_impl(const CsConvGemm* d, cs_stream_t stream, int omap_f, i
     if (!f16x3 || p.act == CS_ACT_GEGLU || (narrow ? (p.cout & 3) : p.cout % 224) || !p.splitk_ws || !al16(p.splitk_ws) ||
         p.splitk > 64)
       return CS_EINVAL;
-    if ((p.ldo & 3) || !al16(p.out) || (p.bias && !al16(p.bias)) || (p.scale && (!al16(p.scale) || !al16(p.shift))) ||
-        (p.rowvec && ((p.ldrv & 3) || !al16(p.rowvec))) || (p.res && ((p.ldr & 3) || !al16(p.res))))
-      return CS_EINVAL;
+    if (!cs_epilogue_vec4(p)) return CS_EINVAL;          // (cout % 4 == 0: checked above)
     const int64_t nk = (int64_t)p.kd * p.kh * p.kw * ((p.cin + 15) / 16);
     if (p.splitk > nk) return CS_EINVAL;
     CsConvGemm part = p;
@@ -1397,9 +1383,8 @@ __global__ __launch_bounds__(256) void up2_reduce_scatter_kernel(const float* __
 }
 
 bool up2_ok(const CsConvGemm& p) {
-  return p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 && p.sw == 1 && p.pd == 1 && p.ph == 1 &&
-         p.pw == 1 && (p.ud | p.uh | p.uw) != 0 && p.ud >= 0 && p.ud <= 1 && p.uh >= 0 && p.uh <= 1 && p.uw >= 0 &&
-         p.uw <= 1 && p.dout == (p.din << p.ud) && p.hout == (p.hin << p.uh) && p.wout == (p.win << p.uw) &&
+  return cs_k333(p) && cs_stride1(p) && cs_pads1(p) && !cs_no_upsample(p) && p.ud >= 0 && p.ud <= 1 && p.uh >= 0 &&
+         p.uh <= 1 && p.uw >= 0 && p.uw <= 1 && p.dout == (p.din << p.ud) && p.hout == (p.hin << p.uh) && p.wout == (p.win << p.uw) &&
          !p.res && !p.rowvec && !p.scale && p.act != CS_ACT_GEGLU && (p.cout & 3) == 0 && (p.ldo & 3) == 0 &&
          p.splitk <= 1;
 }

@@ -1369,11 +1369,7 @@ int launch16(const CsConvGemm& p, int M, int splits, hipStream_t stream, int oma
   const int64_t x_bytes = ((x_rows - 1) * p.lda + p.cin) * (PRE ? 2 : 4);
   const int64_t w_bytes = (int64_t)p.kd * p.kh * p.kw * kg_per_tap * p.cout * 16;
   if (w_bytes > 0xFFE00000LL) return CS_EINVAL;      // activations: per-workgroup windows, no 4 GiB limit
-  // float4 epilogue needs 16-byte aligned rows in every operand it touches
-  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  const int vec = (p.cout % 4 == 0) && (p.ldo % 4 == 0) && al16(p.out) && (!p.bias || al16(p.bias)) &&
-                  (!p.scale || (al16(p.scale) && al16(p.shift))) &&
-                  (!p.rowvec || (p.ldrv % 4 == 0 && al16(p.rowvec))) && (!p.res || (p.ldr % 4 == 0 && al16(p.res)));
+  const int vec = cs_epilogue_vec4(p);
   if (p.act == CS_ACT_GEGLU) {
     // fused gate: needs the float4 epilogue, whole [x | gate] column groups per wave and no other epilogue terms
     constexpr int WCOLS = 32 * WNB;
@@ -1417,72 +1413,139 @@ __global__ __launch_bounds__(256) void pack_f16x3_kernel(const float* __restrict
   }
 }
 
-}  // namespace
+// The instantiation of conv_gemm_f16x3_kernel a launch runs: the kernel's nine template arguments
+struct F16x3Variant {
+  int wmb, wnb, waves_m, waves_n;
+  bool pre;
+  int slab;
+  bool pair;
+  int tpk;
+  bool pw;
+};
 
-// Will this descriptor run the four-taps-per-kd slab kernel (the 3x2x2 / 2x2x2 kernels of the Upsample convs folded onto
-// the source grid)?  One rule for the dispatch below and for cs_conv_gemm_up2, which lets the classes store straight
-// into the doubled grid only on that kernel.  CS_NO_SLAB4=1 keeps them on the per-tap gather (A/B runs, and the
-// reference of the equality test).
-bool cs_f16x3_slab4_ok(const CsConvGemm& p, int tile, int splits) {
-#ifdef CS_NO_SLAB
-  return false;
-#else
-  // (splits < 0: the geometry alone -- the K-sliced class batch of small launches, cs_conv_gemm_up2, r5)
-  return !cs_debug()->no_slab4 && p.a_format == 0 && (tile == 4 || tile == 6) && splits <= 1 && p.kh == 2 && p.kw == 2 &&
-         (p.kd == 2 || p.kd == 3) && p.sd == 1 && p.sh == 1 && p.sw == 1 && p.ud == 0 && p.uh == 0 && p.uw == 0 &&
-         (unsigned)p.pd <= 1u && (unsigned)p.ph <= 1u && (unsigned)p.pw <= 1u && (p.kd == 2 || p.pd == 1) &&
-         p.din == p.dout && p.hin == p.hout && p.win == p.wout && p.win <= 32 &&
-         (256 + 2LL * p.hin * p.win + 2 * p.win + 32) * p.lda * 4 < 0x7FF00000LL;
-#endif
+constexpr uint32_t variant_key(const F16x3Variant& v) {
+  return (uint32_t)(v.wmb | v.wnb << 2 | v.waves_m << 5 | v.waves_n << 9 | v.pre << 11 | (v.slab / 32) << 12 | v.pair << 14 |
+                    v.tpk << 15 | v.pw << 19);
 }
+
+using Launch16 = int (*)(const CsConvGemm&, int, int, hipStream_t, int, int, const CsClsBatch*, const CsFuseK*, int, int);
+struct VariantRow {
+  uint32_t key;
+  Launch16 fn;
+};
+template <int WMB, int WNB, int WAVES_M, int WAVES_N, bool PRE, int SLAB = 0, bool PAIR = false, int TPK = 9, bool PW = false>
+constexpr VariantRow launch16_row() {
+  return {variant_key({WMB, WNB, WAVES_M, WAVES_N, PRE, SLAB, PAIR, TPK, PW}),
+          &launch16<WMB, WNB, WAVES_M, WAVES_N, PRE, SLAB, PAIR, TPK, PW>};
+}
+
+// ONE launch table: every instantiation of the kernel, once.  What cs_f16x3_variant names and this table lacks is refused.
+const VariantRow VARIANTS[] = {
+    // per-tap gather: fp32 operand (in-loop split), pre-split operand, interleaved pair
+    launch16_row<2, 2, 2, 2, false>(), launch16_row<1, 7, 4, 1, false>(), launch16_row<1, 1, 2, 2, false>(),
+    launch16_row<1, 7, 8, 1, false>(),
+    launch16_row<1, 4, 8, 1, false>(),      // 256x128: the VQ decoder's 128- / 256-channel convs
+    launch16_row<1, 2, 8, 1, false>(),      // 256x64:  its 64-channel convs
+    launch16_row<2, 2, 2, 2, true>(), launch16_row<1, 7, 4, 1, true>(), launch16_row<1, 1, 2, 2, true>(),
+    launch16_row<1, 7, 8, 1, true>(), launch16_row<1, 4, 8, 1, true>(), launch16_row<1, 2, 8, 1, true>(),
+    launch16_row<2, 2, 2, 2, false, 0, true>(), launch16_row<1, 7, 4, 1, false, 0, true>(),
+    launch16_row<1, 1, 2, 2, false, 0, true>(), launch16_row<1, 7, 8, 1, false, 0, true>(),
+    launch16_row<1, 4, 8, 1, false, 0, true>(), launch16_row<1, 2, 8, 1, false, 0, true>(),
+    // pointwise (no source-row tables): fp32 operand, interleaved pair
+    launch16_row<2, 2, 2, 2, false, 0, false, 9, true>(), launch16_row<1, 7, 4, 1, false, 0, false, 9, true>(),
+    launch16_row<1, 1, 2, 2, false, 0, false, 9, true>(), launch16_row<1, 7, 8, 1, false, 0, false, 9, true>(),
+    launch16_row<1, 4, 8, 1, false, 0, false, 9, true>(), launch16_row<1, 2, 8, 1, false, 0, false, 9, true>(),
+    launch16_row<2, 2, 2, 2, false, 0, true, 9, true>(), launch16_row<1, 7, 4, 1, false, 0, true, 9, true>(),
+    launch16_row<1, 1, 2, 2, false, 0, true, 9, true>(), launch16_row<1, 7, 8, 1, false, 0, true, 9, true>(),
+    // nine-tap slab (3x3x3, stride 1, "same" padding: the A operand comes from a slab shared by the nine (kh, kw) taps of each
+    // kd, see the kernel's header): fp32 operand, then pre-split
+    launch16_row<1, 7, 4, 1, false, 32>(),      // r3: small batches (128-row tiles, K slices)
+    launch16_row<1, 7, 8, 1, false, 32>(), launch16_row<1, 4, 8, 1, false, 32>(), launch16_row<1, 2, 8, 1, false, 32>(),
+    launch16_row<1, 2, 8, 1, false, 64>(),      // the decoder's 64^3 level
+    launch16_row<1, 7, 4, 1, true, 32>(), launch16_row<1, 7, 8, 1, true, 32>(), launch16_row<1, 4, 8, 1, true, 32>(),
+    launch16_row<1, 2, 8, 1, true, 32>(), launch16_row<1, 2, 8, 1, true, 64>(),
+    // (512 x 64 / 512 x 128, two row blocks per wave: pre-split operands only -- with the in-loop fp32 -> hi/lo conversion two
+    // row blocks x nine unrolled taps spill)
+    launch16_row<2, 2, 8, 1, true, 32>(), launch16_row<2, 2, 8, 1, true, 64>(), launch16_row<2, 4, 8, 1, true, 32>(),
+    // r3: four-tap slab, the 3x2x2 / 2x2x2 kernels of the Upsample convs folded onto the source grid (cs_conv_gemm_up2)
+    launch16_row<1, 7, 8, 1, false, 32, false, 4>(), launch16_row<1, 4, 8, 1, false, 32, false, 4>(),
+    // r5: three-tap slab, the Winograd-W position GEMMs (256x224: the UNet's widths; 256x128 / 256x64: the VQ decoder's)
+    launch16_row<1, 7, 8, 1, true, 32, false, 3>(), launch16_row<1, 4, 8, 1, true, 32, false, 3>(),
+    launch16_row<1, 2, 8, 1, true, 32, false, 3>(),
+};
+
+}  // namespace
 
 // r5: is this the geometry of a Winograd-W position GEMM -- a 3x3x1 kernel over (D, H, W/2), stride 1, pads 1 / 1 / 0, same
 // size out as in (cs_conv_gemm, a_format = 3, builds such a descriptor over the four stacked transformed operands)?
 bool cs_f16x3_wino_geom(const CsConvGemm& p) {
-  return p.kd == 3 && p.kh == 3 && p.kw == 1 && p.sd == 1 && p.sh == 1 && p.sw == 1 && p.pd == 1 && p.ph == 1 && p.pw == 0 &&
-         p.ud == 0 && p.uh == 0 && p.uw == 0 && p.din == p.dout && p.hin == p.hout && p.win == p.wout && p.win <= 32 &&
-         (512 + 2LL * p.hin * p.win + 2 * p.win + 32) * p.lda * 4 < 0x7FF00000LL;
+  return p.kd == 3 && p.kh == 3 && p.kw == 1 && cs_stride1(p) && p.pd == 1 && p.ph == 1 && p.pw == 0 && cs_no_upsample(p) &&
+         cs_same_extent(p) && p.win <= 32 && cs_slab_window_ok(p, 512, p.win);
 }
 
-// Line width of the A slab (32 / 64) the dispatch below stages for this descriptor on `tile` with `splits` K slices, 0 = the
-// per-tap gather.  ONE rule: the dispatch asks it, and so does cs_conv_gemm_launch_info (what the hosts' per-kernel
-// accounting reads instead of mirroring this file).
-int cs_f16x3_slab_width(const CsConvGemm& p, int tile, int splits) {
-#ifdef CS_NO_SLAB
-  return 0;
+// ONE rule: the variant this descriptor runs on `tile` with `splits` K slices, false = refused.  The dispatch below asks it,
+// and so do cs_f16x3_slab_width / cs_f16x3_slab4_ok (what cs_gemm.hip plans with and cs_conv_gemm_launch_info reports).
+// omap_f bit 4: the launch covers Winograd-W position classes stacked along the batch; cls_sliced: all parity classes of a
+// folded Upsample conv x K slices in one launch (omap_f bit 3).
+static bool cs_f16x3_variant(const CsConvGemm& p, int tile, int splits, int omap_f, bool cls_sliced, F16x3Variant* out) {
+#ifdef CS_NO_SLAB      // (A/B timing builds: the per-tap gather everywhere)
+  const bool slabs = false;
 #else
+  const bool slabs = true;
+#endif
+  const CsDebug* dbg = cs_debug();
   if (splits < 1) splits = 1;
-  if (p.a_format == 2) return 0;                                   // interleaved pairs: gather path only
-  if (p.a_format == 0 && cs_f16x3_slab4_ok(p, tile, splits)) return 32;      // folded Upsample classes: four taps per kd
-#ifndef CS_NO_SLAB
-  if (cs_f16x3_wino_geom(p)) {                                               // Winograd-W position GEMMs: three taps per kd
-    const int64_t nsc = 3LL * ((p.cin + 15) / 16);
-    const bool ok = splits == 1 || ((nsc + splits - 1) / splits) * splits * 10 <= nsc * 11;
-    return (p.a_format == 1 && (tile == 4 || tile == 6 || tile == 7) && ok) ? 32 : 0;
+  const bool pre = p.a_format == 1, pair = p.a_format == 2;
+  const bool geom9 = slabs && cs_conv333_s1(p) && cs_pads1(p) && cs_same_extent(p) && p.win <= 64 &&
+                     cs_slab_window_ok(p, 512, p.win);
+  // tiles 8 / 9 (512 x 64 / 512 x 128) exist for the nine-tap slab on pre-split operands only; elsewhere they run as 7 / 6
+  if (tile == 8 && !(geom9 && splits == 1 && pre)) tile = 7;
+  if (tile == 9 && !(geom9 && splits == 1 && p.win <= 32 && pre)) tile = 6;
+  const bool t46 = tile == 4 || tile == 6;
+  const int64_t nsc = 3LL * ((p.cin + 15) / 16);      // super-chunks of the three- and nine-tap slabs
+  int slab = 0, tpk = 9;
+  if (slabs && pre && cs_f16x3_wino_geom(p) && (t46 || tile == 7) && cs_slices_pad_ok(nsc, splits)) {
+    slab = 32, tpk = 3;
+  } else if (slabs && !dbg->no_slab4 && p.a_format == 0 && t46 && (cls_sliced || splits == 1) && p.kh == 2 && p.kw == 2 &&
+             (p.kd == 2 || p.kd == 3) && cs_stride1(p) && cs_no_upsample(p) && (unsigned)p.pd <= 1u && (unsigned)p.ph <= 1u &&
+             (unsigned)p.pw <= 1u && (p.kd == 2 || p.pd == 1) && cs_same_extent(p) && p.win <= 32 &&
+             cs_slab_window_ok(p, 256, p.win)) {
+    // (CsDebug.no_slab4 keeps the folded Upsample classes on the per-tap gather: A/B runs, the reference of the equality test)
+    slab = 32, tpk = 4;
+  } else if (geom9 && !pair && (tile == 2 || t46 || tile == 7 || tile == 8 || tile == 9) &&
+             (splits == 1 || tile == 2 || t46 || tile == 7) && (p.win <= 32 || tile == 7 || tile == 8) &&
+             cs_slices_pad_ok(nsc, splits)) {
+    slab = (tile == 7 || tile == 8) && p.win > 32 ? 64 : 32;
   }
-#endif
-  const bool geom0 = p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 && p.sw == 1 && p.pd == 1 && p.ph == 1 &&
-                     p.pw == 1 && p.ud == 0 && p.uh == 0 && p.uw == 0 && p.din == p.dout && p.hin == p.hout &&
-                     p.win == p.wout && p.win <= 64 && (512 + 2LL * p.hin * p.win + 2 * p.win + 32) * p.lda * 4 < 0x7FF00000LL;
-  // tiles 8 / 9 (512 x 64 / 512 x 128: two row blocks per wave) exist for the slab path on pre-split operands only (with the
-  // in-loop fp32 -> hi/lo conversion two row blocks x nine unrolled taps spill); elsewhere they run as 7 / 6
-  if (tile == 8 && !(geom0 && splits == 1 && p.a_format == 1)) tile = 7;
-  if (tile == 9 && !(geom0 && splits == 1 && p.win <= 32 && p.a_format == 1)) tile = 6;
-  const bool geom = (splits == 1 || tile == 4 || tile == 2 || tile == 6 || tile == 7) && geom0 &&
-                    (p.win <= 32 || tile == 7 || tile == 8);
-  // K slices of the slab kernel are whole super-chunks (nine taps): take it only where that granularity pads the slices
-  // by at most a tenth (42 super-chunks over 32 slices would leave a third of the workgroups idle)
-  const int64_t nsc_all = 3LL * ((p.cin + 15) / 16);
-  const bool slices_ok = splits == 1 || ((nsc_all + splits - 1) / splits) * splits * 10 <= nsc_all * 11;
-  if (!(geom && slices_ok)) return 0;
-  switch (tile) {
-    case 2: case 4: case 6: return 32;
-    case 7: return p.win <= 32 ? 32 : 64;
-    case 8: return p.a_format == 1 ? (p.win <= 32 ? 32 : 64) : 0;
-    case 9: return p.a_format == 1 ? 32 : 0;
-    default: return 0;
-  }
-#endif
+  // the stacked Winograd-W positions exist on the three-tap slab kernel only -- it alone selects the position's weight image:
+  // a launch the slab rules send back to the per-tap gather (a badly padded slice count), which would read image 0 for
+  // every position, is refused, not run
+  if (pre && (omap_f & 16) && !slab) return false;
+  // pointwise (1x1x1, stride 1, no upsampling): no source-row tables; CsDebug.no_pw for A/B runs.  (The pair's pointwise
+  // kernels exist on tiles 1 - 4 only; on 6 / 7 it runs the table-driven one.)
+  const bool pw = !pre && !dbg->no_pw && (!pair || tile <= 4) && p.kd == 1 && p.kh == 1 && p.kw == 1 && cs_stride1(p) &&
+                  cs_no_upsample(p) && p.pd == 0 && p.ph == 0 && p.pw == 0 &&
+                  (int64_t)p.dout * p.hout * p.wout == (int64_t)p.din * p.hin * p.win && 256LL * p.lda * 4 < 0x7FF00000LL;
+  // tile code -> <WMB, WNB, WAVES_M, WAVES_N>: BM = 32 WMB WAVES_M rows, BN = 32 WNB WAVES_N columns
+  static const int dims[10][4] = {{0}, {2, 2, 2, 2}, {1, 7, 4, 1}, {1, 1, 2, 2}, {1, 7, 8, 1}, {0}, {1, 4, 8, 1}, {1, 2, 8, 1},
+                                  {2, 2, 8, 1}, {2, 4, 8, 1}};
+  if (tile < 1 || tile > 9 || !dims[tile][0]) return false;
+  *out = {dims[tile][0], dims[tile][1], dims[tile][2], dims[tile][3], pre, slab, pair, tpk, pw};
+  return true;
+}
+
+// Will this descriptor run the four-taps-per-kd slab kernel?  cs_conv_gemm_up2 lets the classes store straight into the
+// doubled grid only on that kernel.  (splits < 0: the geometry alone -- the K-sliced class batch of small launches, r5)
+bool cs_f16x3_slab4_ok(const CsConvGemm& p, int tile, int splits) {
+  F16x3Variant v;
+  return cs_f16x3_variant(p, tile, splits, 0, splits < 0, &v) && v.tpk == 4;
+}
+
+// Line width of the A slab (32 / 64) the dispatch stages for this descriptor on `tile` with `splits` K slices, 0 = the
+// per-tap gather (what the hosts' per-kernel accounting reads through cs_conv_gemm_launch_info)
+int cs_f16x3_slab_width(const CsConvGemm& p, int tile, int splits) {
+  F16x3Variant v;
+  return cs_f16x3_variant(p, tile, splits, 0, false, &v) ? v.slab : 0;
 }
 
 // called from cs_conv_gemm (cs_gemm.hip) when desc->math == CS_MATH_F16X3; arguments already validated.
@@ -1496,11 +1559,13 @@ int cs_conv_gemm_f16x3_dispatch(const CsConvGemm& p_in, int M, int tile, int spl
   if (u_count != 0 && !(p.a_format == 1 && cs_f16x3_wino_geom(p) && (omap_f & 16))) return CS_EINVAL;
   if (splits < 1) splits = 1;
   const bool cls_sliced = (omap_f & 8) != 0;           // r5: all parity classes x K slices in one launch, partial tiles out
-  if (cls_sliced && (splits < 2 || ncls < 2 || p.a_format != 0 || (tile != 4 && tile != 6) || !cs_f16x3_slab4_ok(p, tile, -1) ||
-                     p.bias || p.res || p.rowvec || p.scale || p.act != CS_ACT_NONE || p.gn_part || p.out_format))
+  F16x3Variant v;
+  if (!cs_f16x3_variant(p, tile, splits, omap_f, cls_sliced, &v)) return CS_EINVAL;
+  if (cls_sliced && (splits < 2 || ncls < 2 || p.bias || p.res || p.rowvec || p.scale || p.act != CS_ACT_NONE || p.gn_part ||
+                     p.out_format))
     return CS_EINVAL;
-  // (omap_f bit 4, r5: the launch covers omap_p Winograd-W position classes stacked along the batch -- no scatter)
-  if ((omap_f & 15) && !cls_sliced && !cs_f16x3_slab4_ok(p, tile, splits)) return CS_EINVAL;
+  // the scattered store / class batch: four-tap slab kernel only, asked on its own tiles
+  if ((omap_f & 15) && (v.tpk != 4 || (tile != 4 && tile != 6))) return CS_EINVAL;
   CsClsBatch cb;
   memset(&cb, 0, sizeof(cb));
   if (ncls > 1) {
@@ -1520,127 +1585,27 @@ int cs_conv_gemm_f16x3_dispatch(const CsConvGemm& p_in, int M, int tile, int spl
   // 16-bit row deltas: the farthest tap is (kd-1) planes + (kh-1) rows + (kw-1) voxels from the window origin
   if ((int64_t)(p.kd - 1) * p.hin * p.win + (int64_t)(p.kh - 1) * p.win + p.kw > 32000) return CS_EINVAL;
   if (((uintptr_t)p.w & 15) || ((uintptr_t)p.w_lo & 15)) return CS_EINVAL;
-  // tiles 8 / 9 (512 x 64 / 512 x 128: two row blocks per wave) exist for the slab path only; elsewhere they run as 7 / 6
-  const bool slab_geom0 = p.kd == 3 && p.kh == 3 && p.kw == 3 && p.sd == 1 && p.sh == 1 &&
-                          p.sw == 1 && p.pd == 1 && p.ph == 1 && p.pw == 1 && p.ud == 0 && p.uh == 0 && p.uw == 0 &&
-                          p.din == p.dout && p.hin == p.hout && p.win == p.wout && p.win <= 64 &&
-                          (512 + 2LL * p.hin * p.win + 2 * p.win + 32) * p.lda * 4 < 0x7FF00000LL;
-  // (pre-split operands only: with the in-loop fp32 -> hi/lo conversion two row blocks x nine unrolled taps spill)
-  if (tile == 8 && !(slab_geom0 && splits == 1 && p.a_format == 1)) tile = 7;
-  if (tile == 9 && !(slab_geom0 && splits == 1 && p.win <= 32 && p.a_format == 1)) tile = 6;
-  const bool slab_geom = cs_f16x3_slab_width(p, tile, splits) != 0 && !cs_f16x3_slab4_ok(p, tile, splits);   // (the one rule, above)
-  const bool slab_slices_ok = true;
   if (p.a_format == 1) {
     if (!p.x_lo || ((uintptr_t)p.x_lo & 15) || (p.cin & 7) || (p.lda & 7)) return CS_EINVAL;
-#ifndef CS_NO_SLAB
-    if (cs_f16x3_wino_geom(p) && (tile == 4 || tile == 6 || tile == 7) && cs_f16x3_slab_width(p, tile, splits) == 32) {
-      const int ncls = (omap_f & 16) ? omap_p : 0;
-      if (ncls > 1 && (((M + 255) / 256) % ncls || M % 256)) return CS_EINVAL;     // whole row tiles per class
-      // (256x224: the UNet's widths; 256x128 / 256x64: the VQ decoder's)
-      if (tile == 4) return launch16<1, 7, 8, 1, true, 32, false, 3>(p, M, splits, s, 0, ncls, nullptr, nullptr, u_base, u_count);
-      if (tile == 6) return launch16<1, 4, 8, 1, true, 32, false, 3>(p, M, splits, s, 0, ncls, nullptr, nullptr, u_base, u_count);
-      return launch16<1, 2, 8, 1, true, 32, false, 3>(p, M, splits, s, 0, ncls, nullptr, nullptr, u_base, u_count);
-    }
-    if (slab_geom && slab_slices_ok) {
-      switch (tile) {
-        case 2: return launch16<1, 7, 4, 1, true, 32>(p, M, splits, s, 0, 0, nullptr, fuse);    // r3: small batches (128-row tiles, K slices)
-        case 4: return launch16<1, 7, 8, 1, true, 32>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 6: return launch16<1, 4, 8, 1, true, 32>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 7: return p.win <= 32 ? launch16<1, 2, 8, 1, true, 32>(p, M, splits, s, 0, 0, nullptr, fuse)
-                                   : launch16<1, 2, 8, 1, true, 64>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 8: return p.win <= 32 ? launch16<2, 2, 8, 1, true, 32>(p, M, splits, s, 0, 0, nullptr, fuse)
-                                   : launch16<2, 2, 8, 1, true, 64>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 9: return launch16<2, 4, 8, 1, true, 32>(p, M, splits, s, 0, 0, nullptr, fuse);
-        default: break;
-      }
-    }
-#endif
-    // the stacked Winograd-W positions (omap_f bit 4) exist on the three-tap slab kernel only -- it alone selects the position's
-    // weight image: a launch that kernel does not take (a slice count cs_f16x3_slab_width sends back to the per-tap gather,
-    // which would read image 0 for every position) is refused, not run
-    if (omap_f & 16) return CS_EINVAL;
-    if (tile == 8) tile = 7;      // (only reachable in -DCS_NO_SLAB builds)
-    if (tile == 9) tile = 6;
-    switch (tile) {
-      case 1: return launch16<2, 2, 2, 2, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 2: return launch16<1, 7, 4, 1, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 3: return launch16<1, 1, 2, 2, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 4: return launch16<1, 7, 8, 1, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 6: return launch16<1, 4, 8, 1, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 7: return launch16<1, 2, 8, 1, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      default: return CS_EINVAL;
-    }
-  }
-  // pointwise (1x1x1, stride 1, no upsampling): no source-row tables (template argument PW); CS_NO_PW=1 for A/B runs
-  const bool pw = !cs_debug()->no_pw && p.kd == 1 && p.kh == 1 && p.kw == 1 && p.sd == 1 && p.sh == 1 && p.sw == 1 &&
-                  p.ud == 0 && p.uh == 0 && p.uw == 0 && p.pd == 0 && p.ph == 0 && p.pw == 0 &&
-                  (int64_t)p.dout * p.hout * p.wout == (int64_t)p.din * p.hin * p.win &&
-                  256LL * p.lda * 4 < 0x7FF00000LL;
-  if (p.a_format == 2) {      // interleaved operand pair: same addressing as fp32, no conversion in the K loop
+  } else if (p.a_format == 2) {      // interleaved operand pair: same addressing as fp32, no conversion in the K loop
     if ((p.cin & 15) || (p.lda & 15)) return CS_EINVAL;
-    if (tile == 8) tile = 7;
-    if (tile == 9) tile = 6;
-    if (pw) {
-      switch (tile) {
-        case 1: return launch16<2, 2, 2, 2, false, 0, true, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 2: return launch16<1, 7, 4, 1, false, 0, true, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 3: return launch16<1, 1, 2, 2, false, 0, true, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-        case 4: return launch16<1, 7, 8, 1, false, 0, true, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-        default: break;
-      }
+  } else if (p.a_format != 0) {
+    return CS_EINVAL;
+  }
+  Launch16 fn = nullptr;
+  for (const VariantRow& r : VARIANTS)
+    if (r.key == variant_key(v)) {
+      fn = r.fn;
+      break;
     }
-    switch (tile) {
-      case 1: return launch16<2, 2, 2, 2, false, 0, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 2: return launch16<1, 7, 4, 1, false, 0, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 3: return launch16<1, 1, 2, 2, false, 0, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 4: return launch16<1, 7, 8, 1, false, 0, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 6: return launch16<1, 4, 8, 1, false, 0, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 7: return launch16<1, 2, 8, 1, false, 0, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      default: return CS_EINVAL;
-    }
+  if (!fn) return CS_EINVAL;
+  if (v.tpk == 3) {
+    const int npos = (omap_f & 16) ? omap_p : 0;
+    if (npos > 1 && (((M + 255) / 256) % npos || M % 256)) return CS_EINVAL;     // whole row tiles per class
+    return fn(p, M, splits, s, 0, npos, nullptr, nullptr, u_base, u_count);
   }
-  if (p.a_format != 0) return CS_EINVAL;
-  // r3: the 3x2x2 / 2x2x2 kernels of the Upsample convs folded onto the source grid (cs_conv_gemm_up2): slab path with
-  // four taps per kd
-  if (cs_f16x3_slab4_ok(p, tile, cls_sliced ? -1 : splits)) {
-    if (tile == 4) return launch16<1, 7, 8, 1, false, 32, false, 4>(p, M, splits, s, omap_f, omap_p, &cb);
-    return launch16<1, 4, 8, 1, false, 32, false, 4>(p, M, splits, s, omap_f, omap_p, &cb);
-  }
-#ifndef CS_NO_SLAB      // (A/B timing builds: -DCS_NO_SLAB keeps the per-tap gather everywhere)
-  // 3x3x3, stride 1, "same" padding, no upsampling, one K slice, 256-row tiles: the A operand comes from a slab
-  // shared by the nine (kh, kw) taps of each kd (see the kernel's header)
-  const bool slab = slab_geom && slab_slices_ok;
-  if (slab) {
-    switch (tile) {
-      case 2: return launch16<1, 7, 4, 1, false, 32>(p, M, splits, s, 0, 0, nullptr, fuse);   // small batches: 128-row tiles, K slices
-      case 4: return launch16<1, 7, 8, 1, false, 32>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 6: return launch16<1, 4, 8, 1, false, 32>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 7: return p.win <= 32 ? launch16<1, 2, 8, 1, false, 32>(p, M, splits, s, 0, 0, nullptr, fuse)
-                                 : launch16<1, 2, 8, 1, false, 64>(p, M, splits, s, 0, 0, nullptr, fuse);   // the decoder's 64^3 level
-      default: break;
-    }
-  }
-#endif
-  if (pw) {
-    switch (tile) {
-      case 1: return launch16<2, 2, 2, 2, false, 0, false, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 2: return launch16<1, 7, 4, 1, false, 0, false, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 3: return launch16<1, 1, 2, 2, false, 0, false, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 4: return launch16<1, 7, 8, 1, false, 0, false, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 6: return launch16<1, 4, 8, 1, false, 0, false, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      case 7: return launch16<1, 2, 8, 1, false, 0, false, 9, true>(p, M, splits, s, 0, 0, nullptr, fuse);
-      default: break;
-    }
-  }
-  switch (tile) {
-    case 1: return launch16<2, 2, 2, 2, false>(p, M, splits, s, 0, 0, nullptr, fuse);
-    case 2: return launch16<1, 7, 4, 1, false>(p, M, splits, s, 0, 0, nullptr, fuse);
-    case 3: return launch16<1, 1, 2, 2, false>(p, M, splits, s, 0, 0, nullptr, fuse);
-    case 4: return launch16<1, 7, 8, 1, false>(p, M, splits, s, 0, 0, nullptr, fuse);
-    case 6: return launch16<1, 4, 8, 1, false>(p, M, splits, s, 0, 0, nullptr, fuse);     // 256x128: the VQ decoder's 128- / 256-channel convs
-    case 7: return launch16<1, 2, 8, 1, false>(p, M, splits, s, 0, 0, nullptr, fuse);     // 256x64:  its 64-channel convs
-    default: return CS_EINVAL;
-  }
+  if (v.tpk == 4) return fn(p, M, splits, s, omap_f, omap_p, &cb, nullptr, 0, 0);
+  return fn(p, M, splits, s, 0, 0, nullptr, fuse, 0, 0);
 }
 
 extern "C" int cs_pack_weight_f16x3(const float* w_torch, void* w_hi, void* w_lo, int cout, int cin, int taps,
