@@ -24,6 +24,7 @@ CS_ENOMEM = -12
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GELU, ACT_GEGLU = 0, 1, 2, 3, 4
 MATH_FP32, MATH_F16X3 = 0, 1
 VQ_ST_ROWS = 256     # CS_VQ_ST_ROWS: rows per workgroup of cs_vq_quantize_st (its scratch holds one double per tile)
+PAIR_CHUNK, PAIR_PARTIAL_BYTES = 2048, 32     # CS_PAIR_CHUNK / CS_PAIR_PARTIAL_BYTES: cs_pair_stats' workspace is one partial per chunk
 MATH_F16 = 2        # attention only: plain fp16 operands (reduced precision, opt-in)
 # The numerics mode model classes start in: F16X3 (fp32-grade, the benchmarked mode) unless CS_MATH=fp32 asks for the
 # fp32-input MFMA kernels.  `set_math()` switches per model.
@@ -225,6 +226,8 @@ SIGNATURES = {
     "cs_vqvae_pack": (_i, [C.c_void_p, _f, _f, _s]),
     "cs_vqvae_workspace_bytes": (_l, [C.c_void_p, _i]),
     "cs_vqvae_decode": (_i, [C.c_void_p, _f, _f, _f, _f, _i, _i, _f, _f, _l, _s]),
+    "cs_q_sample": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _l, _l, _s]),
+    "cs_pair_stats": (_i, [_f, _f, _i, _l, _l, _l, _f, _f, _fl, _fl, _f, _l, _s]),
     "cs_abi_version": (_i, []),
 }
 

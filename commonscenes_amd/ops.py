@@ -1576,3 +1576,89 @@ def log_softmax(x: Tensor) -> Tensor:
     _, _, ldy = rows_ld(y, "y")
     L.check(L.load().cs_log_softmax(x.data_ptr(), y.data_ptr(), m, c, ldx, ldy, _stream()), "cs_log_softmax")
     return y
+
+
+def _index_range_ok(idx: Tensor, n: int) -> bool:
+    """host-side range check of a device-resident index vector (one read-back of its min / max; no device-side assert)"""
+    lo, hi = torch.aminmax(idx)
+    return int(lo) >= 0 and int(hi) < n
+
+
+def q_sample(x0: Tensor, noise: Tensor, t: Tensor, sa: Tensor, s1: Tensor, src: Optional[Tensor] = None,
+             nsrc: Optional[Tensor] = None) -> Tensor:
+    """cs_q_sample: out[r] = sa[t[r]] * x0[src[r]] + s1[t[r]] * noise[nsrc[r]] (two rounded multiplies, one rounded add).
+    x0 [n0, ...], noise [n1, ...] with equal trailing shapes, t int64 [rows], sa / s1 fp32 [T] device tables, src / nsrc int32
+    [rows] row maps (None = identity).  Returns [rows, ...].  The indices are range-checked here, on the host."""
+    _chk(x0, "x_start"); _chk(noise, "noise"); _chk(t, "t", torch.int64); _chk(sa, "sa"); _chk(s1, "s1")
+    if t.dim() != 1 or t.numel() == 0:
+        raise L.CsError("q_sample: t must be a non-empty vector")
+    if x0.dim() < 1 or tuple(x0.shape[1:]) != tuple(noise.shape[1:]) or x0.shape[0] == 0 or noise.shape[0] == 0:
+        raise L.CsError(f"q_sample: x_start {tuple(x0.shape)} and noise {tuple(noise.shape)} must share their row shape")
+    if sa.dim() != 1 or sa.shape != s1.shape or sa.numel() == 0:
+        raise L.CsError("q_sample: sa and s1 must be equally long 1-d tables")
+    x0 = x0.contiguous(); noise = noise.contiguous(); t = t.contiguous(); sa = sa.contiguous(); s1 = s1.contiguous()
+    rows, T = int(t.numel()), int(sa.numel())
+    n0, n1 = int(x0.shape[0]), int(noise.shape[0])
+    per = x0.numel() // n0
+    if per == 0:
+        raise L.CsError("q_sample: empty rows")
+    if not _index_range_ok(t, T):
+        raise L.CsError(f"q_sample failed: invalid argument (a timestep outside [0, {T}))")
+    for m, n, name in ((src, n0, "src"), (nsrc, n1, "nsrc")):
+        if m is None:
+            if n < rows:
+                raise L.CsError(f"q_sample failed: invalid argument ({rows} rows from {n} source rows without a {name} map)")
+            continue
+        _chk(m, name, torch.int32)
+        if m.dim() != 1 or m.numel() != rows:
+            raise L.CsError(f"q_sample: {name} must hold one int32 per output row")
+        if not _index_range_ok(m, n):
+            raise L.CsError(f"q_sample failed: invalid argument ({name} outside [0, {n}))")
+    src = None if src is None else src.contiguous()
+    nsrc = None if nsrc is None else nsrc.contiguous()
+    out = torch.empty((rows, *x0.shape[1:]), dtype=torch.float32, device=x0.device)
+    L.check(L.load().cs_q_sample(x0.data_ptr(), noise.data_ptr(), out.data_ptr(), t.data_ptr(), sa.data_ptr(), s1.data_ptr(),
+                                 _ptr(src), _ptr(nsrc), rows, per, T, n0, n1, _stream()), "cs_q_sample")
+    return out
+
+
+def _sample_rows(t: Tensor, name: str) -> Tuple[int, int, int]:
+    """`t` as nb sample rows [nb, per] with row stride ld: dim 0 is the sample, everything behind it must be dense."""
+    if t.dim() < 1 or t.shape[0] == 0:
+        raise L.CsError(f"{name}: needs a leading sample dimension")
+    nb = int(t.shape[0])
+    per = t.numel() // nb
+    if per == 0:
+        raise L.CsError(f"{name}: empty samples")
+    if not t[0].is_contiguous():
+        raise L.CsError(f"{name}: every sample must be dense {tuple(t.shape)} {t.stride()}")
+    ld = int(t.stride(0)) if nb > 1 else per
+    if ld < per:
+        raise L.CsError(f"{name}: overlapping samples {tuple(t.shape)} {t.stride()}")
+    return nb, per, ld
+
+
+def pair_stats(a: Tensor, b: Tensor, thr_a: Optional[float] = None, thr_b: Optional[float] = None,
+               want_sums: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """cs_pair_stats in one pass over a, b [nb, ...] (sample rows may be `ld` views of a wider buffer):
+    sums fp64 [nb, 2] = {sum d^2, sum |d|} with d = fp32(a - b) (None when want_sums is False), counts int64 [nb, 2] =
+    {inter, union} of occ_a = !(a > thr_a), occ_b = !(b > thr_b) (None unless both thresholds are given).  Deterministic, and
+    independent of nb and of a sample's position in the batch."""
+    _chk(a, "a"); _chk(b, "b")
+    if (thr_a is None) != (thr_b is None):
+        raise L.CsError("pair_stats: give both thresholds or neither")
+    if tuple(a.shape) != tuple(b.shape):
+        raise L.CsError(f"pair_stats: shapes differ {tuple(a.shape)} vs {tuple(b.shape)}")
+    nb, per, lda = _sample_rows(a, "a")
+    _, _, ldb = _sample_rows(b, "b")
+    want_counts = thr_a is not None
+    if not (want_sums or want_counts):
+        raise L.CsError("pair_stats: nothing to compute")
+    sums = torch.empty((nb, 2), dtype=torch.float64, device=a.device) if want_sums else None
+    counts = torch.empty((nb, 2), dtype=torch.int64, device=a.device) if want_counts else None
+    chunks = (per + L.PAIR_CHUNK - 1) // L.PAIR_CHUNK
+    ws = torch.empty((nb * chunks * L.PAIR_PARTIAL_BYTES // 8,), dtype=torch.float64, device=a.device)
+    L.check(L.load().cs_pair_stats(a.data_ptr(), b.data_ptr(), nb, per, lda, ldb, _ptr(sums), _ptr(counts),
+                                   float(thr_a) if want_counts else 0.0, float(thr_b) if want_counts else 0.0,
+                                   ws.data_ptr(), ws.numel() * 8, _stream()), "cs_pair_stats")
+    return sums, counts

@@ -157,8 +157,13 @@ class SDFusionText2ShapeModel:
     # ---- schedule (:152-236) ----
     def init_diffusion_params(self, uc_scale=3., df_model_params=None):
         self.parameterization = "eps"
+        self.learn_logvar = False                                       # :165-170
+        self.v_posterior = 0.
+        self.original_elbo_weight = 0.
+        self.l_simple_weight = 1.
         self.register_schedule(timesteps=df_model_params.timesteps, linear_start=df_model_params.linear_start,
                                linear_end=df_model_params.linear_end)
+        self.logvar = torch.full(fill_value=0., size=(self.num_timesteps,))      # :178-179
         self.uc_scale = uc_scale
         self.scale = uc_scale     # the reference reads an undefined self.scale when uc_scale=None (:474)
 
@@ -176,6 +181,23 @@ class SDFusionText2ShapeModel:
         self.alphas_cumprod_prev = to_torch(alphas_cumprod_prev)
         self.sqrt_alphas_cumprod = to_torch(np.sqrt(alphas_cumprod))
         self.sqrt_one_minus_alphas_cumprod = to_torch(np.sqrt(1. - alphas_cumprod))
+        # :210-235, the tables p_losses and the posterior read: float64 numpy, rounded to fp32 where the reference rounds
+        self.log_one_minus_alphas_cumprod = to_torch(np.log(1. - alphas_cumprod))
+        self.sqrt_recip_alphas_cumprod = to_torch(np.sqrt(1. / alphas_cumprod))
+        self.sqrt_recipm1_alphas_cumprod = to_torch(np.sqrt(1. / alphas_cumprod - 1))
+        v_posterior = getattr(self, "v_posterior", 0.)
+        posterior_variance = (1 - v_posterior) * betas * (1. - alphas_cumprod_prev) / (1. - alphas_cumprod) + v_posterior * betas
+        self.posterior_variance = to_torch(posterior_variance)
+        self.posterior_log_variance_clipped = to_torch(np.log(np.maximum(posterior_variance, 1e-20)))
+        self.posterior_mean_coef1 = to_torch(betas * np.sqrt(alphas_cumprod_prev) / (1. - alphas_cumprod))
+        self.posterior_mean_coef2 = to_torch((1. - alphas_cumprod_prev) * np.sqrt(alphas) / (1. - alphas_cumprod))
+        if getattr(self, "parameterization", "eps") != "eps":
+            raise NotImplementedError("only the 'eps' parameterisation is shipped")
+        lvlb_weights = self.betas ** 2 / (2 * self.posterior_variance * to_torch(alphas) * (1 - self.alphas_cumprod))   # fp32 ops
+        lvlb_weights[0] = lvlb_weights[1]
+        self.lvlb_weights = lvlb_weights
+        assert not torch.isnan(self.lvlb_weights).all()
+        self._dev_tables = {}         # device copies of the two tables cs_q_sample indexes, made on first use
 
     # ---- reference surface ----
     def set_input(self, input=None, max_sample=None):
@@ -209,6 +231,185 @@ class SDFusionText2ShapeModel:
     def apply_model_cfg(self, x, t, c_in):
         """[eps_uc; eps_c] for the guidance pair batch (ddim.py:206-209) without duplicating (x, t)."""
         return self.df.forward_cfg(x, t, c_in)
+
+    # ---- training-time losses, forward only (:268-345) --------------------------------------------------------------
+    def _q_tables(self):
+        dev = torch.device(self.device)
+        key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+        tb = self._dev_tables.get(key)
+        if tb is None:
+            tb = self._dev_tables[key] = (self.sqrt_alphas_cumprod.to(dev).contiguous(),
+                                          self.sqrt_one_minus_alphas_cumprod.to(dev).contiguous())
+        return tb
+
+    def _t_dev(self, t) -> Tensor:
+        return torch.as_tensor(t, dtype=torch.int64).to(self.device).reshape(-1)
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None, src=None, nsrc=None):
+        """:268-272: sqrt_alphas_cumprod[t] * x_start + sqrt_one_minus_alphas_cumprod[t] * noise with a per-sample timestep,
+        one cs_q_sample launch (the reference's three roundings per element).  Extension: `src` / `nsrc` int32 row maps."""
+        x_start = x_start.to(device=self.device, dtype=torch.float32)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        sa, s1 = self._q_tables()
+        return ops.q_sample(x_start, noise.to(device=self.device, dtype=torch.float32), self._t_dev(t), sa, s1, src, nsrc)
+
+    @torch.no_grad()
+    def get_loss(self, pred, target, loss_type='l2', mean=True):
+        """:293-306, value only.  mean=True: the fp32 scalar of F.mse_loss / (target - pred).abs().mean().  mean=False: the
+        reference returns the element-wise map, and its one caller reduces it with .mean([1, 2, 3, 4]) at once (:328, :339);
+        here that per-sample mean is returned directly, fp32 [B].  Either way one cs_pair_stats launch: fp64 sums in a fixed
+        order, divided once and rounded to fp32 once."""
+        if loss_type not in ('l1', 'l2'):
+            raise NotImplementedError(f"unknown loss type '{loss_type}'")
+        pred = pred.to(device=self.device, dtype=torch.float32)
+        target = target.to(device=self.device, dtype=torch.float32)
+        sums, _ = ops.pair_stats(target, pred)
+        col = sums[:, 0 if loss_type == 'l2' else 1]
+        per = pred.numel() // pred.shape[0]
+        if mean:
+            return (col.sum() / float(pred.numel())).to(torch.float32)
+        return (col / float(per)).to(torch.float32)
+
+    def _loss_dict(self, loss_simple: Tensor, t: Tensor):
+        """:328-343 from the per-sample loss_simple [B] (fp32) on: a handful of fp32 operations over B numbers, evaluated on the
+        host in the reference's order (the schedule tables live there)."""
+        ls = loss_simple.detach().to("cpu", torch.float32)
+        tc = t.detach().to("cpu")
+        loss_dict = {"loss_simple": ls.mean()}
+        logvar_t = self.logvar[tc]
+        loss = ls / torch.exp(logvar_t) + logvar_t
+        if self.learn_logvar:
+            raise NotImplementedError("learn_logvar is not shipped")
+        loss = self.l_simple_weight * loss.mean()
+        loss_vlb = (self.lvlb_weights[tc] * ls).mean()
+        loss_dict["loss_vlb"] = loss_vlb
+        loss = loss + self.original_elbo_weight * loss_vlb
+        loss_dict["loss_total"] = loss.clone().detach().mean()
+        return loss.to(self.device), {k: v.to(self.device) for k, v in loss_dict.items()}
+
+    @torch.no_grad()
+    def p_losses(self, x_start, cond, t, noise=None):
+        """:311-345, forward only: (x_noisy, target, loss, loss_dict) with loss_simple / loss_vlb / loss_total as fp32 0-dim
+        tensors.  x_start is the latent [B, 3, 16, 16, 16], t int64 [B]."""
+        if self.parameterization != "eps":
+            raise NotImplementedError("only the 'eps' parameterisation is shipped")
+        self.switch_eval()
+        x_start = x_start.to(device=self.device, dtype=torch.float32)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        noise = noise.to(device=self.device, dtype=torch.float32)
+        t = self._t_dev(t)
+        x_noisy = self.q_sample(x_start=x_start, t=t, noise=noise)
+        model_output = self._apply_checked(x_noisy, t, cond)
+        self.last_model_output = model_output
+        target = noise
+        loss_simple = self.get_loss(model_output, target, mean=False)
+        loss, loss_dict = self._loss_dict(loss_simple, t)
+        return x_noisy, target, loss, loss_dict
+
+    def _apply_checked(self, x_noisy, t, cond):
+        """apply_model under the F16X3 overflow policy of the samplers (see _sample_minibatch)."""
+        def run():
+            if hasattr(self.df, "reset_run_cache"):
+                self.df.reset_run_cache()
+            ops.clear_status(self.device)
+            out = self.apply_model(x_noisy, t, cond)
+            ops.check_overflow(self.device, "denoising loss (UNet)")
+            return out
+        try:
+            try:
+                return run()
+            except L.CsSplitKTimeout as e:
+                _log.warning("fused split-K reduce timed out: re-running with no_fused_reduce=1 (%s)", e)
+                L.debug_set(no_fused_reduce=1)
+                self.fell_back["splitk_two_kernel"] = True
+                return run()
+        except L.CsOverflowError:
+            if self.overflow_policy != "fp32" or getattr(self.df, "math", None) != L.MATH_F16X3:
+                raise
+            _log.warning("F16X3 activation overflow in the UNet: this model continues on the fp32-input MFMA kernels")
+            self.df.set_math("fp32")
+            self._df_fell_back = True
+            self.fell_back["unet_fp32"] = True
+            return run()
+
+    @torch.no_grad()
+    def denoising_loss_table(self, x, c, timesteps, noise=None, seed=None, batch=64, encoded=False, return_meta=False):
+        """Extension (ours, not in the reference): the training loss of a held-out set at fixed timesteps.
+
+        x: [N, 1, 64, 64, 64] SDFs, encoded with vqvae.encode_no_quant (raises when the checkpoint has no encoder), or with
+        encoded=True the latents [N, 3, 16, 16, 16].  c: the condition of each shape, per the conditioning key.  Every shape is
+        evaluated at every entry of `timesteps` (K of them): row k * N + n of the sweep is shape n at timesteps[k], noised by
+        cs_q_sample through row maps (the latents are never repeated) and run through the UNet in launches of at most
+        `batch` rows.  noise: [N, ...] shared over the timesteps, [N, K, ...] one per cell, or None = drawn from a device
+        generator seeded with `seed` (None: the clock, like the reference's sampling).
+        Returns {'per_sample': fp64 [N, K] per-shape loss_simple, 'loss_simple': fp32 [K], 'loss_vlb': fp32 [K], 'timesteps':
+        int64 [K], 'fell_back': ...}: column k holds what p_losses reports for all N shapes at t = timesteps[k]."""
+        if self.parameterization != "eps":
+            raise NotImplementedError("only the 'eps' parameterisation is shipped")
+        self.switch_eval()
+        ts = torch.as_tensor(timesteps, dtype=torch.int64).reshape(-1).cpu()
+        K = int(ts.numel())
+        if K == 0 or int(ts.min()) < 0 or int(ts.max()) >= self.num_timesteps:
+            raise ValueError(f"timesteps must be a non-empty list inside [0, {self.num_timesteps})")
+        if int(batch) < 1:
+            raise ValueError("batch must be at least 1")
+        x = x.to(device=self.device, dtype=torch.float32)
+        if encoded:
+            z = x.contiguous()
+        else:
+            if not getattr(self.vqvae, "has_encoder", False):
+                raise RuntimeError("denoising_loss_table: the VQ-VAE checkpoint has no encoder (encoder.* / quant_conv.*); "
+                                   "pass latents with encoded=True")
+            z = self.vqvae.encode_no_quant(x)
+        N = int(z.shape[0])
+        if tuple(z.shape[1:]) != tuple(self.z_shape) or N == 0:
+            raise ValueError(f"latents {tuple(z.shape)} do not match the model's {self.z_shape}")
+        c = c.to(device=self.device, dtype=torch.float32)
+        if self.df.conditioning_key == "concat":
+            c = c.reshape(N, -1, *self.z_shape[1:])
+        if c.shape[0] != N:
+            raise ValueError(f"{N} shapes but {c.shape[0]} conditions")
+        if noise is None:
+            g = torch.Generator(device=self.device)
+            g.manual_seed(int(time.time()) if seed is None else int(seed))
+            noise = torch.randn((N, K, *self.z_shape), generator=g, device=self.device, dtype=torch.float32)
+        noise = noise.to(device=self.device, dtype=torch.float32)
+        if tuple(noise.shape) == (N, *self.z_shape):
+            per_cell = False
+        elif tuple(noise.shape) == (N, K, *self.z_shape):
+            per_cell = True
+        else:
+            raise ValueError(f"noise {tuple(noise.shape)}: expected [N, ...] or [N, K, ...] with N = {N}, K = {K}")
+        nz = noise.reshape(-1, *self.z_shape).contiguous()
+        rows = N * K
+        r = torch.arange(rows)
+        n_of, k_of = r % N, r // N
+        src_all = n_of.to(torch.int32).to(self.device)
+        nsrc_all = (n_of * K + k_of if per_cell else n_of).to(torch.int32).to(self.device)
+        t_all = ts[k_of].to(self.device)
+        sa, s1 = self._q_tables()
+        per = z.numel() // N
+        means = torch.empty((rows,), dtype=torch.float64, device=self.device)
+        for lo in range(0, rows, int(batch)):
+            hi = min(rows, lo + int(batch))
+            x_noisy = ops.q_sample(z, nz, t_all[lo:hi], sa, s1, src_all[lo:hi], nsrc_all[lo:hi])
+            eps = self._apply_checked(x_noisy, t_all[lo:hi], c[src_all[lo:hi].long()])
+            target = nz[nsrc_all[lo:hi].long()]
+            sums, _ = ops.pair_stats(target, eps)
+            means[lo:hi] = sums[:, 0] / float(per)
+        m = means.cpu().reshape(K, N)
+        ls = m.to(torch.float32)                     # p_losses' per-sample loss_simple: the fp64 mean rounded once
+        # (row by row, the very reductions of _loss_dict: column k is bit for bit what p_losses reports at timesteps[k])
+        out = {"per_sample": m.t().contiguous(), "loss_simple": torch.stack([ls[k].mean() for k in range(K)]),
+               "loss_vlb": torch.stack([(self.lvlb_weights[ts[k].expand(N)] * ls[k]).mean() for k in range(K)]),
+               "timesteps": ts.clone(),
+               "fell_back": dict(self.fell_back), "any_fell_back": any(self.fell_back.values())}
+        self.last_meta = {"fell_back": dict(self.fell_back), "any_fell_back": any(self.fell_back.values()),
+                          "launch_sizes": [min(int(batch), rows - lo) for lo in range(0, rows, int(batch))]}
+        return (out, self.last_meta) if return_meta else out
 
     # ---- F16X3 overflow policy -------------------------------------------------------------------------------------
     # CS_MATH_F16X3 carries activations as fp16 pairs of a * 16: |a| >= ~4094 cannot be represented.  Every F16X3

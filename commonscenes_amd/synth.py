@@ -177,3 +177,16 @@ def sdf_volume(variant: int = 0, res: int = 64) -> torch.Tensor:
     db = outside + np.minimum(np.maximum(q[0], np.maximum(q[1], q[2])), 0.0)
     d = np.clip(np.minimum(ds, db), -0.2, 0.2)
     return torch.from_numpy(d.astype(np.float32).reshape(1, 1, res, res, res))
+
+
+def iou_case(thres: float):
+    """Two batches of three 64^3 volumes for the IoU counts (tests/golden/eval_losses.npz, fixture (c)): sample 0 =
+    sdf_volume(0) against sdf_volume(1) with one NaN voxel and one voxel exactly at fp32(thres); sample 1 = the two volumes
+    swapped; sample 2 = two all-free volumes (empty union)."""
+    v0, v1 = sdf_volume(0), sdf_volume(1)
+    a = torch.cat([v0, v1, torch.full_like(v0, 0.2)], dim=0)
+    b = torch.cat([v1, v0, torch.full_like(v0, 0.15)], dim=0).clone()
+    b[0, 0, 10, 20, 30] = float("nan")
+    b[0, 0, 40, 41, 42] = float(np.float32(thres))
+    b[2] += float(np.float32(max(thres, 0.0)))          # stays free for every threshold
+    return a, b

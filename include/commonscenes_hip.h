@@ -999,6 +999,37 @@ int cs_vqvae_decode(const cs_vqvae* u, const void* arena, const float* latent_nc
                     int64_t* code_indices, int nb, int quantize, int32_t* status, void* workspace,
                     int64_t workspace_bytes, cs_stream_t stream);
 
+/*
+ * Held-out checkpoint evaluation (csrc/cs_eval.hip): the glue of SDFusionText2ShapeModel.p_losses
+ * (sdfusion_txt2shape_model.py:268-345) and of VQVAEModel.test_iou / VQLoss (vqvae_model.py:107-168,
+ * diff_utils/util.py:111-130, losses.py:63-83).  Forward only.
+ *
+ * cs_q_sample: out[r][0:per] = sa[t[r]] * x0[src[r]][0:per] + s1[t[r]] * noise[nsrc[r]][0:per], r < rows -- two fp32
+ * multiplies and one fp32 add, each rounded (never an fma): the reference's three ATen ops.
+ *   t [rows] int64 (device), sa / s1 [T] fp32 (device): sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod
+ *   src / nsrc [rows] int32 (device) or NULL = the identity: row maps into x0 [x0_rows][per] / noise [noise_rows][per], so
+ *   N shapes x K timesteps are noised without K copies of the latents.  All rows dense (row stride per).
+ * CS_EINVAL for what the host can see (NULL, sizes <= 0, an identity map over fewer source rows than `rows`).  The indices
+ * live on the device: a caller checks their range before the call (ops.q_sample does); the kernel reads nothing out of
+ * bounds for a bad one and fills that output row with NaN.  16-byte accesses when per % 4 == 0 and the bases are aligned.
+ *
+ * cs_pair_stats: one pass over a, b [nb][per] fp32 (row strides lda, ldb >= per); per sample, with d = fp32(a - b):
+ *   sums   [nb][2] double  {sum d^2, sum |d|}       (d^2 is exact in fp64: only the summation rounds)      or NULL
+ *   counts [nb][2] int64   {inter, union} of the occupancy masks occ_a = !(a > thr_a), occ_b = !(b > thr_b)  or NULL
+ *                          (util.py:116-122 builds exactly these masks -- a NaN voxel ends up occupied there too)
+ * At least one of sums / counts.  Deterministic: a sample is cut into chunks of CS_PAIR_CHUNK floats, one workgroup and one
+ * partial per (sample, chunk) in `workspace` (nb * ceil(per / CS_PAIR_CHUNK) * CS_PAIR_PARTIAL_BYTES bytes, 8-byte aligned;
+ * CS_ENOMEM when smaller), every thread owns fixed elements, every fold has a fixed order, no atomics: a sample's result does
+ * not depend on nb, on its position in the batch or on the alignment of its rows, and two runs are bit-identical.
+ */
+#define CS_PAIR_CHUNK 2048
+#define CS_PAIR_PARTIAL_BYTES 32
+int cs_q_sample(const float* x0, const float* noise, float* out, const int64_t* t, const float* sa, const float* s1,
+                const int32_t* src, const int32_t* nsrc, int64_t rows, int64_t per, int T, int64_t x0_rows,
+                int64_t noise_rows, cs_stream_t stream);
+int cs_pair_stats(const float* a, const float* b, int nb, int64_t per, int64_t lda, int64_t ldb, double* sums,
+                  int64_t* counts, float thr_a, float thr_b, void* workspace, int64_t workspace_bytes, cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

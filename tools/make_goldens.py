@@ -921,6 +921,90 @@ def g_constraints():
          cond_dropped_small=np.int64(d7 + dm), **arrs)
 
 
+EVAL_T = (0, 1, 500, 999)
+EVAL_THRES = (0.0, 0.02, -0.05)
+
+
+def g_eval_losses(tmp: Path):
+    """tests/golden/eval_losses.npz: what a held-out evaluation reports, from the reference on the CPU.
+    (a) SDFusionText2ShapeModel (sdfusion_txt2shape_model.py:159-345, reduced-width UNet): the schedule tables and p_losses
+        at B = 4, t = (0, 1, 500, 999); (b) the VQ-VAE's reconstruction IoU (vqvae_model.py:110-136 spelled out: the model class
+        itself needs a renderer) and VQLoss's log; (c) diff_utils/util.py:111-130 iou() on synth.iou_case inputs."""
+    from model.diff_utils.util import iou
+    from model.losses import VQLoss
+    out = {}
+    # ---- (a)
+    model, _, _, _ = build_ref_scene(tmp, small=True)
+    D = model.Diff
+    for k in ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
+              "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_variance",
+              "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2", "lvlb_weights", "logvar"):
+        out["tab_" + k] = getattr(D, k).detach().clone()
+    out["consts"] = np.array([float(D.learn_logvar), D.v_posterior, D.original_elbo_weight, D.l_simple_weight], np.float64)
+    B = len(EVAL_T)
+    x0 = synth.gaussian_like("eval:x0", (B, 3, 16, 16, 16), scale=0.8)
+    noise = synth.gaussian_like("eval:noise", (B, 3, 16, 16, 16))
+    cond = synth.gaussian_like("eval:c", (B, 1, 1280))
+    t = torch.tensor(EVAL_T, dtype=torch.long)
+    rec = {}
+    am = D.apply_model
+
+    def am_rec(*a, **k):
+        rec["eps"] = am(*a, **k)
+        return rec["eps"]
+    D.apply_model = am_rec
+    t0 = time.time()
+    with torch.no_grad():
+        x_noisy, target, loss, ld = D.p_losses(x0, cond, t, noise=noise)
+        eps = rec["eps"]
+        per_sample = D.get_loss(eps, target, mean=False).mean([1, 2, 3, 4])
+    print(f"[eval_losses] reference p_losses {time.time() - t0:.1f}s  {dict((k, float(v)) for k, v in ld.items())}")
+    assert torch.equal(target, noise) and sorted(ld) == ["loss_simple", "loss_total", "loss_vlb"]
+    r = eps.double().flatten(1).norm(dim=1) / (eps.double() - noise.double()).flatten(1).norm(dim=1)
+    chk = lambda v: np.array([float(v.double().sum()), float(v.double().abs().sum())], np.float64)
+    out.update(t=t, x0_chk=chk(x0), noise_chk=chk(noise), cond_chk=chk(cond), x_noisy=x_noisy, eps=eps,
+               loss_simple_per_sample=per_sample, loss=loss.reshape(1), r=r,
+               loss_keys=np.array(sorted(ld)), loss_vals=torch.stack([ld[k].reshape(()) for k in sorted(ld)]))
+    # ---- (b)
+    vq, _ = build_ref_vqvae_full()
+    x = torch.cat([synth.sdf_volume(0), synth.sdf_volume(1)], dim=0)
+    lc = vq_conf().get("lossconfig")
+    cw = float(lc.params.codebook_weight) if lc is not None else 1.0
+    with torch.no_grad():
+        z = vq(x, forward_no_quant=True, encode_only=True)
+        xr = vq.decode_no_quant(z)
+        _, _, info = vq.quantize(z, is_voxel=True)
+        dec, diff = vq(x)
+        _, log = VQLoss(codebook_weight=cw)(diff, x, dec)
+    rows = []
+    for thr in EVAL_THRES:
+        v = iou(x, xr, thr)
+        og, orr = x <= 0.0, xr <= thr
+        inter, union = (og & orr).flatten(1).sum(1), (og | orr).flatten(1).sum(1)
+        assert torch.equal(v, inter / (union + 1e-12))
+        near = ((xr - thr).abs() < 1e-4).flatten(1).sum(1)
+        assert bool((near * 1000 <= union).all()), (thr, near, union)       # the tolerance cannot hide a wrong kernel
+        rows.append((v, inter, union, near))
+        print(f"[eval_losses] thres {thr}: iou {v.tolist()} inter {inter.tolist()} union {union.tolist()} near {near.tolist()}")
+    out.update(vq_thres=np.array(EVAL_THRES, np.float64), vq_iou=torch.stack([r_[0] for r_ in rows]),
+               vq_inter=torch.stack([r_[1] for r_ in rows]), vq_union=torch.stack([r_[2] for r_ in rows]),
+               vq_n_near=torch.stack([r_[3] for r_ in rows]), vq_indices=info[2], vq_codebook_weight=np.float64(cw),
+               vq_log_keys=np.array(sorted(log)), vq_log_vals=torch.stack([log[k].reshape(()) for k in sorted(log)]),
+               vq_x_chk=chk(x))
+    # ---- (c)
+    ci, cc = [], []
+    for thr in EVAL_THRES:
+        a, b = synth.iou_case(thr)
+        v = iou(a, b, thr)
+        ma, mb = ~(a > 0.0), ~(b > np.float32(thr))
+        inter, union = (ma & mb).flatten(1).sum(1), (ma | mb).flatten(1).sum(1)
+        assert torch.equal(v, inter / (union + 1e-12)) and int(union[2]) == 0 and float(v[2]) == 0.0
+        ci.append(v)
+        cc.append(torch.stack([inter, union], 1))
+    out.update(case_iou=torch.stack(ci), case_counts=torch.stack(cc))
+    save("eval_losses", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -930,7 +1014,7 @@ def main():
     todo = a.only or ["schedule", "unet_small", "unet_full", "ddim_small", "ddim_full", "vq", "gcn", "e2e",
                       "unet_concat_small", "unet_concat_full", "ddim_concat_small", "gcn_concat", "e2e_concat", "box",
                       "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode", "shape_metrics",
-                      "constraints"]
+                      "constraints", "eval_losses"]
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name in todo:
@@ -985,6 +1069,8 @@ def main():
                 g_shape_metrics()
             elif name == "constraints":
                 g_constraints()
+            elif name == "eval_losses":
+                g_eval_losses(tmp)
             else:
                 raise SystemExit(f"unknown fixture {name}")
 
