@@ -83,19 +83,27 @@ class DDIMSampler(object):
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1.,
                noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
                log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None,
-               mm_cls_free=False, **kwargs):
+               mm_cls_free=False, q_noise=None, **kwargs):
+        """ddim.py:60-123.  `mask` / `x0` (shape completion, ddim.py:158-161): before every step the region where mask is 1
+        is replaced by q_sample(x0, t), so only the rest is generated.  x0 [n, C, ...] and mask [m, 1 or C, ...] hold one
+        row per sample, or ONE row shared by the whole batch (the reference's broadcast), or any number of rows addressed
+        through the int32 row maps `x0_src` / `mask_src` [batch_size] (extension: K completions of one object share its
+        rows).  Extension `q_noise`: None draws the q_sample noise with torch.randn on the device once per step
+        (torch.manual_seed reproduces a run); a tensor [n_steps, batch_size, C, ...] supplies iteration i's noise as
+        q_noise[i]."""
         if isinstance(conditioning, dict):
             raise NotImplementedError("dict conditioning (ddim.py:85-88) is not on the rel2shape path: pass the "
                                       "conditioning tensor ([B,1,1280] crossattn / [B,1,16,16,16] concat)")
         if conditioning is not None:
             if conditioning.shape[0] != batch_size:
                 print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
-        for name, val, ok in (("mask", mask, None), ("x0", x0, None), ("score_corrector", score_corrector, None)):
-            if val is not ok:
-                raise NotImplementedError(f"DDIMSampler.sample({name}=...) is not on the rel2shape path")
+        if score_corrector is not None:
+            raise NotImplementedError("DDIMSampler.sample(score_corrector=...) is not on the rel2shape / shape_comp paths")
         if quantize_x0 or mm_cls_free or noise_dropout > 0. or temperature != 1.:
             raise NotImplementedError("quantize_x0 / mm_cls_free / noise_dropout / temperature are not on the "
-                                      "rel2shape path (sdfusion_txt2shape_model.py:498-507)")
+                                      "rel2shape / shape_comp paths (sdfusion_txt2shape_model.py:498-507)")
+        if mask is not None:
+            assert x0 is not None                                        # ddim.py:159
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         if len(shape) == 4:
             C_, D, H, W = shape
@@ -109,11 +117,52 @@ class DDIMSampler(object):
                                   log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning,
-                                  max_steps=kwargs.get("max_steps"))
+                                  max_steps=kwargs.get("max_steps"), mask=mask, x0=x0, q_noise=q_noise,
+                                  x0_src=kwargs.get("x0_src"), mask_src=kwargs.get("mask_src"))
+
+    def _masked_setup(self, shape, device, mask, x0, q_noise, x0_src, mask_src, n_steps):
+        """What the masked step needs, made ONCE per run: x0 / mask as fp32 device tensors, the two q_sample tables, the
+        row maps (range-checked here, so the loop reads nothing back), the per-step noise stack."""
+        assert x0 is not None                                            # ddim.py:159
+        b = int(shape[0])
+        x0 = x0.to(device=device, dtype=torch.float32).contiguous()
+        mask = mask.to(device=device, dtype=torch.float32).contiguous()
+        if tuple(x0.shape[1:]) != tuple(shape[1:]):
+            raise ops.L.CsError(f"sample(x0=...): x0 {tuple(x0.shape)} does not hold rows of {tuple(shape[1:])}")
+        if mask.dim() != len(shape) or tuple(mask.shape[2:]) != tuple(shape[2:]) or mask.shape[1] not in (1, shape[1]):
+            raise ops.L.CsError(f"sample(mask=...): mask {tuple(mask.shape)} must be [n, 1 or {shape[1]}, "
+                                f"{', '.join(str(v) for v in shape[2:])}]")
+        maps = []
+        for m, n, name in ((x0_src, int(x0.shape[0]), "x0_src"), (mask_src, int(mask.shape[0]), "mask_src")):
+            if m is None:
+                if n == b:
+                    maps.append(None)
+                    continue
+                if n != 1:
+                    raise ops.L.CsError(f"sample({name[:-4]}=...): {n} rows for a batch of {b}: give one row per sample, "
+                                        f"a single shared row, or the row map {name}")
+                m = torch.zeros((b,), dtype=torch.int32)                 # the reference's broadcast of a single row
+            m = torch.as_tensor(m).to(torch.int32).reshape(-1).cpu()
+            if m.numel() != b or int(m.min()) < 0 or int(m.max()) >= n:
+                raise ops.L.CsError(f"sample({name}=...): needs {b} entries inside [0, {n})")
+            maps.append(m.to(device))
+        tabs = getattr(self.model, "_q_tables", None)
+        if tabs is not None:
+            sa, s1 = tabs()
+        else:     # any model with the two tables the reference's q_sample reads (sdfusion_txt2shape_model.py:268-272)
+            sa = self.model.sqrt_alphas_cumprod.to(device=device, dtype=torch.float32).contiguous()
+            s1 = self.model.sqrt_one_minus_alphas_cumprod.to(device=device, dtype=torch.float32).contiguous()
+        if q_noise is not None:
+            q_noise = q_noise.to(device=device, dtype=torch.float32)
+            if q_noise.dim() != len(shape) + 1 or tuple(q_noise.shape[1:]) != tuple(shape) or q_noise.shape[0] < n_steps:
+                raise ops.L.CsError(f"sample(q_noise=...): expected [{n_steps}, {', '.join(str(v) for v in shape)}], got "
+                                    f"{tuple(q_noise.shape)}")
+        return x0, mask, sa, s1, maps[0], maps[1], q_noise
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, callback=None, img_callback=None, log_every_t=100,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, max_steps=None):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, max_steps=None,
+                      mask=None, x0=None, q_noise=None, x0_src=None, mask_src=None):
         device = self.model.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
@@ -124,14 +173,27 @@ class DDIMSampler(object):
         cfg = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
         # hoisted out of the loop: the conditioning batch [uc; c] never changes (ddim.py:208)
         c_in = torch.cat([unconditional_conditioning, cond]) if cfg else cond
-        if (self.use_graph and img.is_cuda and callback is None and img_callback is None
+        if (self.use_graph and mask is None and img.is_cuda and callback is None and img_callback is None
                 and not np.any(np.asarray(self.ddim_sigmas) != 0.0)):
             return self._graph_sampling(img, c_in, time_range, total_steps, cfg, unconditional_guidance_scale,
                                         log_every_t, max_steps, intermediates)
+        if mask is not None:
+            n_steps = total_steps if max_steps is None else min(int(max_steps), total_steps)
+            x0, mask, sa, s1, src, msrc, q_noise = self._masked_setup(shape, device, mask, x0, q_noise, x0_src, mask_src,
+                                                                      n_steps)
+            own = False       # True while img is this loop's own buffer (not x_T, not an entry of `intermediates`): blend in place
         for i, step in enumerate(time_range):
             if max_steps is not None and i >= max_steps:
                 break
             index = total_steps - i - 1
+            if mask is not None:                                         # ddim.py:158-161
+                if not 0 <= int(step) < int(sa.numel()):
+                    raise ops.L.CsError(f"masked DDIM step: timestep {int(step)} outside [0, {int(sa.numel())})")
+                nz = q_noise[i] if q_noise is not None else torch.randn(shape, device=device)
+                ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+                img = img.contiguous()
+                img = ops.masked_blend(img, x0, mask, nz, ts, sa, s1, src, msrc, out=img if own else None,
+                                       check_indices=False)
             want_p0 = bool(img_callback) or index % log_every_t == 0 or index == total_steps - 1
             img, pred_x0 = self._step(img, c_in, int(step), index, cfg, unconditional_guidance_scale,
                                       want_pred_x0=want_p0)
@@ -139,9 +201,11 @@ class DDIMSampler(object):
                 callback(i)
             if img_callback:
                 img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
+            logged = index % log_every_t == 0 or index == total_steps - 1
+            if logged:
                 intermediates["x_inter"].append(img)
                 intermediates["pred_x0"].append(pred_x0)
+            own = not logged
         return img, intermediates
 
     @torch.no_grad()

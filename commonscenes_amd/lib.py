@@ -228,6 +228,7 @@ SIGNATURES = {
     "cs_vqvae_decode": (_i, [C.c_void_p, _f, _f, _f, _f, _i, _i, _f, _f, _l, _s]),
     "cs_q_sample": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _l, _l, _s]),
     "cs_pair_stats": (_i, [_f, _f, _i, _l, _l, _l, _f, _f, _fl, _fl, _f, _l, _s]),
+    "cs_ddim_masked_blend": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _l, _i, _l, _i, _i, _l, _l, _s]),
     "cs_abi_version": (_i, []),
 }
 

@@ -1622,6 +1622,77 @@ def q_sample(x0: Tensor, noise: Tensor, t: Tensor, sa: Tensor, s1: Tensor, src: 
     return out
 
 
+def masked_blend(img: Tensor, x0: Tensor, mask: Tensor, noise: Tensor, t: Tensor, sa: Tensor, s1: Tensor,
+                 src: Optional[Tensor] = None, msrc: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                 check_indices: bool = True) -> Tensor:
+    """cs_ddim_masked_blend, the masked step of the DDIM loop (samplers/ddim.py:158-161) in one launch:
+        q = sa[t[r]] * x0[src[r]] + s1[t[r]] * noise[r];   out[r] = q * mask[msrc[r]] + (1 - mask[msrc[r]]) * img[r]
+    every product and sum rounded to fp32 as the reference's ATen ops round them.  img / noise [rows, C, ...], x0 [n0, C, ...],
+    mask [n1, 1 or C, ...] with the same trailing shape, t int64 [rows], sa / s1 fp32 [T] device tables, src / msrc int32
+    [rows] row maps (None = identity).  `out` None = a new tensor; `out=img` blends in place.  The indices are range-checked
+    here, on the host (one min / max read-back each); `check_indices=False` is for a caller that has checked them itself --
+    the sampler does, once per run, so its loop stays free of host synchronisation."""
+    tensors = [(img, "img", torch.float32), (x0, "x0", torch.float32), (mask, "mask", torch.float32),
+               (noise, "noise", torch.float32), (t, "t", torch.int64), (sa, "sa", torch.float32), (s1, "s1", torch.float32)]
+    tensors += [(m, name, torch.int32) for m, name in ((src, "src"), (msrc, "msrc")) if m is not None]
+    for v, name, dt in tensors:
+        if v.dtype != dt:
+            raise L.CsError(f"{name}: expected {dt}, got {v.dtype}")
+    if t.dim() != 1 or t.numel() == 0:
+        raise L.CsError("masked_blend: t must be a non-empty vector")
+    rows = int(t.numel())
+    if img.dim() < 2 or img.shape[0] != rows or tuple(noise.shape) != tuple(img.shape):
+        raise L.CsError(f"masked_blend: img {tuple(img.shape)} and noise {tuple(noise.shape)} must both hold one "
+                        f"[C, ...] row per timestep ({rows})")
+    if x0.dim() != img.dim() or tuple(x0.shape[1:]) != tuple(img.shape[1:]) or x0.shape[0] == 0:
+        raise L.CsError(f"masked_blend: x0 {tuple(x0.shape)} must share the row shape of img {tuple(img.shape)}")
+    C_ = int(img.shape[1])
+    if mask.dim() != img.dim() or tuple(mask.shape[2:]) != tuple(img.shape[2:]) or mask.shape[0] == 0:
+        raise L.CsError(f"masked_blend: mask {tuple(mask.shape)} must share the voxel shape of img {tuple(img.shape)}")
+    MC = int(mask.shape[1])
+    if MC != 1 and MC != C_:
+        raise L.CsError(f"masked_blend: the mask has {MC} channels, neither 1 nor {C_}")
+    if sa.dim() != 1 or sa.shape != s1.shape or sa.numel() == 0:
+        raise L.CsError("masked_blend: sa and s1 must be equally long 1-d tables")
+    inner = img.numel() // (rows * C_) if C_ else 0
+    if inner == 0:
+        raise L.CsError("masked_blend: empty rows")
+    if not img.is_contiguous():
+        raise L.CsError("masked_blend: img must be contiguous (it is blended in place)")
+    x0 = x0.contiguous(); mask = mask.contiguous(); noise = noise.contiguous(); t = t.contiguous()
+    sa = sa.contiguous(); s1 = s1.contiguous()
+    T, n0, n1 = int(sa.numel()), int(x0.shape[0]), int(mask.shape[0])
+    if check_indices and not _index_range_ok(t, T):
+        raise L.CsError(f"masked_blend failed: invalid argument (a timestep outside [0, {T}))")
+    for m, n, name in ((src, n0, "src"), (msrc, n1, "msrc")):
+        if m is None:
+            if n < rows:
+                raise L.CsError(f"masked_blend failed: invalid argument ({rows} rows from {n} source rows without a "
+                                f"{name} map)")
+            continue
+        if m.dim() != 1 or m.numel() != rows:
+            raise L.CsError(f"masked_blend: {name} must hold one int32 per output row")
+        if check_indices and not _index_range_ok(m, n):
+            raise L.CsError(f"masked_blend failed: invalid argument ({name} outside [0, {n}))")
+    for v, name, dt in tensors:          # (what the shapes and values say is reported first: it reads the same on any device)
+        _chk(v, name, dt)
+    src = None if src is None else src.contiguous()
+    msrc = None if msrc is None else msrc.contiguous()
+    if out is None:
+        out = torch.empty_like(img)
+    else:
+        _chk(out, "out")
+        if tuple(out.shape) != tuple(img.shape) or not out.is_contiguous():
+            raise L.CsError(f"masked_blend: out {tuple(out.shape)} must be a contiguous tensor shaped like img")
+        for other, name in ((x0, "x0"), (mask, "mask"), (noise, "noise")):
+            if out.untyped_storage().data_ptr() == other.untyped_storage().data_ptr():
+                raise L.CsError(f"masked_blend: out must not share storage with {name}")
+    L.check(L.load().cs_ddim_masked_blend(x0.data_ptr(), noise.data_ptr(), mask.data_ptr(), img.data_ptr(), out.data_ptr(),
+                                          t.data_ptr(), sa.data_ptr(), s1.data_ptr(), _ptr(src), _ptr(msrc), rows, C_, inner,
+                                          MC, T, n0, n1, _stream()), "cs_ddim_masked_blend")
+    return out
+
+
 def _sample_rows(t: Tensor, name: str) -> Tuple[int, int, int]:
     """`t` as nb sample rows [nb, per] with row stride ld: dim 0 is the sample, everything behind it must be dense."""
     if t.dim() < 1 or t.shape[0] == 0:

@@ -418,7 +418,8 @@ class SDFusionText2ShapeModel:
     # 'raise': propagate CsOverflowError.
     overflow_policy = os.environ.get("CS_OVERFLOW_POLICY", "fp32")
 
-    def _sample_minibatch(self, sampler, ddim_steps, shape, c, uc, noise, uc_scale, ddim_eta, max_steps):
+    def _sample_minibatch(self, sampler, ddim_steps, shape, c, uc, noise, uc_scale, ddim_eta, max_steps, **sample_kw):
+        """`sample_kw`: further sampler.sample arguments of this run (shape_comp: mask, x0, q_noise and the row maps)."""
         def run():
             if hasattr(self.df, "reset_run_cache"):
                 self.df.reset_run_cache()           # per-run caches (one-token context vectors) never outlive a run
@@ -428,7 +429,7 @@ class SDFusionText2ShapeModel:
             ops.clear_status(self.device)
             out, _ = sampler.sample(S=ddim_steps, batch_size=c.shape[0], shape=shape, conditioning=c, x_T=noise,
                                     verbose=False, unconditional_guidance_scale=uc_scale,
-                                    unconditional_conditioning=uc, eta=ddim_eta, max_steps=max_steps)
+                                    unconditional_conditioning=uc, eta=ddim_eta, max_steps=max_steps, **sample_kw)
             ops.check_overflow(self.device, "DDIM sampling (UNet)")
             return out
         try:
@@ -710,6 +711,112 @@ class SDFusionText2ShapeModel:
         if return_latents:
             return (self.gen_df, llat, meta) if return_meta else (self.gen_df, llat)
         return (self.gen_df, meta) if return_meta else self.gen_df
+
+    # ---- shape completion (sdfusion_model.py:399-446, on the conditioned model) -----------------------------------------------
+    def _encode_checked(self, x):
+        """vqvae.encode_no_quant under the overflow policy of _decode_checked (raises when the checkpoint has no encoder)."""
+        ops.clear_status(self.device)
+        z = self.vqvae_module.encode_no_quant(x)
+        try:
+            ops.check_overflow(self.device, "VQ-VAE encode")
+        except L.CsOverflowError:
+            if (self.overflow_policy != "fp32" or getattr(self.vqvae, "math", None) != L.MATH_F16X3
+                    or not hasattr(self.vqvae, "set_math")):
+                raise
+            _log.warning("F16X3 activation overflow in the VQ-VAE encoder: this model continues on the fp32-input MFMA kernels")
+            self.vqvae.set_math("fp32")
+            self._vq_fell_back = True
+            self.fell_back["vqvae_fp32"] = True
+            z = self.vqvae_module.encode_no_quant(x)
+        return z
+
+    @torch.no_grad()
+    def shape_comp(self, shape, xyz_dict, cond, uc=None, ngen=1, ddim_steps=100, ddim_eta=0.0, uc_scale=None,
+                   x_T: Optional[Tensor] = None, q_noise: Optional[Tensor] = None, return_latents: bool = False,
+                   return_meta: bool = False):
+        """Shape completion: keep what lies inside the box `xyz_dict` of each SDF, generate the rest under that object's
+        condition.  The reference has this on its unconditional model (sdfusion_model.py:399-446: encode, get_partial_shape,
+        DDIMSampler.sample(x0=z, mask=z_mask), decode_no_quant); here it runs with the object's scene-graph condition and
+        classifier-free guidance, as rel2shape does.
+
+        shape: [N, 1, 64, 64, 64] SDFs (a 4-d input gains a batch axis).  cond / uc: what rel2shape hands the sampler for
+        those N objects (crossattn [N, 1, 1280], or the concat volume); uc=None = the unconditional embedding of the last
+        set_input (`self.uc_rel`).  ngen completions per object.  x_T: [N * ngen, C, d, h, w] start noise (None: drawn
+        fresh per row, as the reference's sampler does); q_noise: [steps, N * ngen, C, d, h, w], the q_sample noise of every
+        step (None: drawn on the device once per step).  Returns [N * ngen, 1, 64, 64, 64] SDFs, object-major (rows
+        n * ngen .. n * ngen + ngen - 1 belong to object n), and sets self.x_part / self.x_missing (visualisation).
+        The known region is re-noised before every step and not after the last one, so in the result it is what the last
+        step made of q_sample(x0, t_min): close to the input there, not equal to it (the reference's behaviour).
+        Rows run in sampler launches of at most `launch_B`; the ngen rows of an object read its latent and mask through row
+        maps.  With q_noise and x_T given, a row's result does not depend on how the rows were sliced (bit for bit when the
+        GEMM plan of the launch is the same, within fp32 summation order otherwise).  Single-rank."""
+        if dist.world()[1] > 1:
+            raise RuntimeError("shape_comp is single-rank (no object sharding): call it on one rank under torch.distributed")
+        ngen = int(ngen)
+        if ngen < 1:
+            raise ValueError("ngen must be at least 1")
+        self.switch_eval()
+        if ddim_steps is None:
+            ddim_steps = self.ddim_steps
+        if uc_scale is None:
+            uc_scale = self.scale
+        if shape.dim() == 4:
+            shape = shape.unsqueeze(0)
+        shape = shape.to(device=self.device, dtype=torch.float32)
+        from .demo_util import get_partial_shape
+        z = self._encode_checked(shape)
+        N = int(z.shape[0])
+        if tuple(z.shape[1:]) != tuple(self.z_shape) or N == 0:
+            raise ValueError(f"latents {tuple(z.shape)} do not match the model's {self.z_shape}")
+        ret = get_partial_shape(shape, xyz_dict=xyz_dict, z=z)
+        z_mask = ret["z_mask"]
+        self.x_part, self.x_missing = ret["shape_part"], ret["shape_missing"]
+        C_, D, H, W = self.z_shape
+        cond = cond.to(device=self.device, dtype=torch.float32)
+        if uc is None:
+            uc = getattr(self, "uc_rel", None)
+            if uc is None:
+                raise ValueError("shape_comp: uc=None needs the unconditional embedding of an earlier set_input (uc_rel)")
+        uc = uc.to(device=self.device, dtype=torch.float32)
+        if self.df.conditioning_key == "concat":
+            cond, uc = cond.reshape(cond.shape[0], -1, D, H, W), uc.reshape(uc.shape[0], -1, D, H, W)
+        if cond.shape[0] != N or uc.shape[0] != N:
+            raise ValueError(f"{N} shapes but {cond.shape[0]} conditions / {uc.shape[0]} unconditional embeddings")
+        rows = N * ngen
+        obj = torch.arange(rows) // ngen                                  # object-major: row r completes object r // ngen
+        if x_T is not None:
+            x_T = x_T.to(device=self.device, dtype=torch.float32)
+            if tuple(x_T.shape) != (rows, C_, D, H, W):
+                raise ValueError(f"x_T {tuple(x_T.shape)}: expected {(rows, C_, D, H, W)}")
+        smp = DDIMSampler(self)
+        smp.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=ddim_eta, verbose=False)
+        n_steps = int(smp.ddim_timesteps.shape[0])
+        if q_noise is not None:
+            q_noise = q_noise.to(device=self.device, dtype=torch.float32)
+            if tuple(q_noise.shape) != (n_steps, rows, C_, D, H, W):
+                raise ValueError(f"q_noise {tuple(q_noise.shape)}: expected {(n_steps, rows, C_, D, H, W)}")
+        lb = int(self.launch_B) if int(self.launch_B) > 0 else max(1, int(self.mini_B))      # (0: the reference's mini-batch)
+        self.last_launch_sizes = []
+        gen, lats = [], []
+        for lo in range(0, rows, lb):
+            hi = min(rows, lo + lb)
+            self.last_launch_sizes.append(hi - lo)
+            o = obj[lo:hi]
+            src = o.to(torch.int32)
+            samples = self._sample_minibatch(
+                smp, ddim_steps, self.z_shape, cond[o.to(self.device)], uc[o.to(self.device)],
+                None if x_T is None else x_T[lo:hi].contiguous(), uc_scale, ddim_eta, None,
+                mask=z_mask, x0=z, x0_src=src, mask_src=src,
+                q_noise=None if q_noise is None else q_noise[:, lo:hi].contiguous())
+            lats.append(samples)
+            gen.append(self._decode_checked(samples))
+        self.last_latents, self.gen_df = torch.cat(lats, dim=0), torch.cat(gen, dim=0)
+        meta = self._meta(ddim_steps, "ddim")
+        meta["ngen"], meta["masked_steps"] = ngen, n_steps
+        out = (self.gen_df, self.last_latents) if return_latents else self.gen_df
+        if return_meta:
+            return (*out, meta) if return_latents else (out, meta)
+        return out
 
     # ---- the other callers of the same sampler (sdfusion_txt2shape_model.py:368-457) -----------------------------------
     # The reference runs these over ALL objects in one sampler call (no mini-batching) with fresh noise per object

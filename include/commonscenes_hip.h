@@ -1030,6 +1030,30 @@ int cs_q_sample(const float* x0, const float* noise, float* out, const int64_t* 
 int cs_pair_stats(const float* a, const float* b, int nb, int64_t per, int64_t lda, int64_t ldb, double* sums,
                   int64_t* counts, float thr_a, float thr_b, void* workspace, int64_t workspace_bytes, cs_stream_t stream);
 
+/*
+ * Shape completion (csrc/cs_complete.hip): the masked step of DDIMSampler.ddim_sampling (samplers/ddim.py:158-161),
+ *   img_orig = model.q_sample(x0, ts);  img = img_orig * mask + (1. - mask) * img
+ * as ONE launch over NCDHW fp32 volumes.  For output row r < rows, channel c < channels, voxel i < inner:
+ *   q   = fadd(fmul(sa[t[r]], x0[src[r]][c][i]), fmul(s1[t[r]], noise[r][c][i]))
+ *   m   = mask[msrc[r]][mc][i]                        mc = c, or 0 when mask_channels == 1
+ *   out[r][c][i] = fadd(fmul(q, m), fmul(fsub(1, m), img[r][c][i]))
+ * five rounded fp32 operations after the q_sample's three, never contracted to an fma: the reference's ATen ops.
+ *   x0 [x0_rows][channels][inner], mask [mask_rows][mask_channels][inner], noise / img / out [rows][channels][inner], all
+ *   dense.  t [rows] int64 (device), sa / s1 [T] fp32 (device) as in cs_q_sample.  src / msrc [rows] int32 (device) or
+ *   NULL = the identity: K completions of one object share its x0 and mask rows without a copy.
+ *   `out` may be `img` (the sampler blends in place: every element is read and written by the same thread); it must not
+ *   overlap x0, noise or mask.
+ * CS_EINVAL for what the host can see (NULL, sizes <= 0, mask_channels neither 1 nor channels, an identity map over fewer
+ * source rows than `rows`).  The indices live on the device: a caller checks their range before the call
+ * (ops.masked_blend does); the kernel reads nothing out of bounds for a bad one and fills that output row with NaN.
+ * 16-byte accesses for every (row, channel) run whose offsets in all five arrays are multiples of 4 floats (and the bases
+ * 16-byte aligned), scalar accesses for the other runs and for the last inner % 4 voxels of each run.
+ */
+int cs_ddim_masked_blend(const float* x0, const float* noise, const float* mask, const float* img, float* out,
+                         const int64_t* t, const float* sa, const float* s1, const int32_t* src, const int32_t* msrc,
+                         int64_t rows, int channels, int64_t inner, int mask_channels, int T, int64_t x0_rows,
+                         int64_t mask_rows, cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

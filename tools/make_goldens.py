@@ -1005,6 +1005,147 @@ def g_eval_losses(tmp: Path):
     save("eval_losses", **out)
 
 
+SHAPE_COMP_BOXES = (
+    {"x": (-1, 1), "y": (-1, 1), "z": (-1, 1)},                     # the full cube
+    {"x": (-3, 0.5), "y": (-0.5, 7), "z": (-1.5, 1.5)},             # bounds outside [-1, 1]: clamped
+    {"x": (0.3, 1), "y": (-0.55, 0.3), "z": (-1, -0.55)},           # 0.3 / -0.55 truncate differently at 16 (10, 3) and 64 (41, 14)
+    {"x": (0.5, 0.5), "y": (-1, 1), "z": (-1, 1)},                  # an empty range
+    {"x": (0, 0.04), "y": (-1, 1), "z": (0, 0.125)},                # single slabs: x at 64 only (empty at 16), z at 16 (4 at 64)
+    {"x": (-1, .25), "y": (-1, 1), "z": (-.5, 1)},                  # the box of the masked trajectory: mean(z_mask) = 0.46875
+    {"x": (0.5, -0.5), "y": (-1, 1), "z": (-1, 1)},                 # an inverted range: empty too
+)
+SHAPE_COMP_TRAJ_BOX = 5
+SHAPE_COMP_E2E_BOX = {"x": (-1, 0.1), "y": (-0.55, 1), "z": (-1, 1)}
+
+
+def _volume_chk(v):
+    """{sum, sum of magnitudes, position-weighted sum} in fp64: the last one moves when a value changes place"""
+    d = v.detach().double().flatten()
+    w = (torch.arange(d.numel(), dtype=torch.float64) % 251.0) + 1.0
+    return np.array([float(d.sum()), float(d.abs().sum()), float((d * w).sum())], np.float64)
+
+
+def _import_ref_demo_util():
+    """model/diff_utils/demo_util.py imports dataset / model-factory packages the tree does not have (upstream leftovers): stub
+    them for the import only.  get_partial_shape itself needs none of them."""
+    names = ["datasets", "datasets.base_dataset", "datasets.dataloader", "models", "models.base_model", "utils", "utils.util"]
+    saved = {n: sys.modules.get(n) for n in names}
+    for n in names:
+        m = mock.MagicMock(name=n)
+        m.__path__ = []
+        sys.modules[n] = m
+    try:
+        import model.diff_utils.demo_util as du
+    finally:
+        for n, m in saved.items():
+            if m is None:
+                sys.modules.pop(n, None)
+            else:
+                sys.modules[n] = m
+    return du
+
+
+class _QNoise:
+    """torch.randn_like as the masked sampler's q_sample calls it (sdfusion_txt2shape_model.py:269), wrapped: call i returns
+    synth.gaussian_like(f"{tag}:q{i}") and is recorded -- the tests rebuild the same tensors, the fixture keeps checksums."""
+
+    def __init__(self, tag):
+        self.tag, self.rec, self._orig = tag, [], torch.randn_like
+
+    def __enter__(self):
+        def randn_like(x, *a, **k):
+            n = synth.gaussian_like(f"{self.tag}:q{len(self.rec)}", tuple(x.shape))
+            self.rec.append(n)
+            return n.clone()
+        torch.randn_like = randn_like
+        return self
+
+    def __exit__(self, *exc):
+        torch.randn_like = self._orig
+        return False
+
+
+def g_shape_comp(tmp: Path):
+    """Shape completion, from the reference on the CPU.  Three files, each under the size limit of a committed file:
+    shape_comp.npz          (a) diff_utils/demo_util.py:172-254 get_partial_shape on SHAPE_COMP_BOXES; (c) the sequence of
+                            sdfusion_model.py:399-446 spelled out with a condition: encode, masks, masked sampling of 2 objects
+                            x 2 completions, decode_no_quant
+    shape_comp_traj_x.npz / shape_comp_traj_pred_x0.npz
+                            (b) DDIMSampler.sample(mask=, x0=) (samplers/ddim.py:158-161): B = 2, S = 6 (7 steps), scale 3,
+                            eta 0, every step's x and pred_x0."""
+    from model.networks.diffusion_networks.samplers.ddim import DDIMSampler
+    du = _import_ref_demo_util()
+    out = {}
+    # ---- (a)
+    vol = torch.cat([synth.sdf_volume(0), synth.sdf_volume(1)], dim=0)
+    zdummy = torch.zeros(2, 3, 16, 16, 16)
+    out["vol_chk"] = _volume_chk(vol)
+    out["boxes"] = np.array([[b["x"], b["y"], b["z"]] for b in SHAPE_COMP_BOXES], np.float64)
+    for i, box in enumerate(SHAPE_COMP_BOXES):
+        ret = du.get_partial_shape(vol, box, z=zdummy)
+        assert sorted(ret) == ["shape_mask", "shape_missing", "shape_part", "z_mask"]
+        assert ret["shape_mask"].dtype == torch.bool and ret["z_mask"].dtype == torch.float32
+        out[f"shape_mask_{i}"], out[f"z_mask_{i}"] = ret["shape_mask"], ret["z_mask"]
+        out[f"part_chk_{i}"], out[f"missing_chk_{i}"] = _volume_chk(ret["shape_part"]), _volume_chk(ret["shape_missing"])
+        print(f"[shape_comp] box {i}: mean(shape_mask) {ret['shape_mask'].float().mean():.6f} mean(z_mask) "
+              f"{ret['z_mask'].mean():.6f}")
+    assert "z_mask" not in du.get_partial_shape(vol, SHAPE_COMP_BOXES[0])
+    # ---- (b)
+    model, _, _, _ = build_ref_scene(tmp, small=True)
+    D = model.Diff
+    B, S = 2, 6
+    x0 = synth.gaussian_like("shape_comp:x0", (B, 3, 16, 16, 16), scale=0.8)
+    c = synth.gaussian_like("shape_comp:c", (B, 1, 1280))
+    uc = synth.gaussian_like("shape_comp:uc", (B, 1, 1280))
+    x_T = synth.gaussian_like("shape_comp:xT", (B, 3, 16, 16, 16))
+    z_mask = du.get_partial_shape(torch.zeros(B, 1, 64, 64, 64), SHAPE_COMP_BOXES[SHAPE_COMP_TRAJ_BOX], z=x0)["z_mask"]
+    assert float(z_mask.mean()) == 0.46875
+    t0 = time.time()
+    with torch.no_grad(), _QNoise("shape_comp") as qn:
+        x, inter = DDIMSampler(D).sample(S=S, batch_size=B, shape=(3, 16, 16, 16), conditioning=c, x0=x0, mask=z_mask,
+                                         x_T=x_T, verbose=False, unconditional_guidance_scale=3.0,
+                                         unconditional_conditioning=uc, eta=0.0, log_every_t=1)
+    xi, pi = inter["x_inter"], inter["pred_x0"]
+    assert len(qn.rec) == 7 and len(xi) == 8 and len(pi) == 8 and torch.equal(xi[-1], x)
+    known = (x - x0).abs()[z_mask.expand_as(x) > 0].max()
+    print(f"[shape_comp] 7 masked reference DDIM steps {time.time() - t0:.1f}s  final rms {x.pow(2).mean().sqrt():.4f}  "
+          f"max |x - x0| over the known region {known:.4f}")
+    traj = dict(S=np.int64(S), steps=np.int64(7), scale=np.float32(3.0), box=np.int64(SHAPE_COMP_TRAJ_BOX),
+                x0_chk=_volume_chk(x0), c_chk=_volume_chk(c), uc_chk=_volume_chk(uc), xT_chk=_volume_chk(x_T),
+                q_chk=np.stack([_volume_chk(n) for n in qn.rec]), known_max_diff=np.float64(known))
+    save("shape_comp_traj_x", x=torch.stack(xi[1:]), **traj)
+    save("shape_comp_traj_pred_x0", pred_x0=torch.stack(pi[1:]))
+    # ---- (c)
+    vq, _ = build_ref_vqvae_full()
+    N, ngen, S2 = 2, 2, 4          # S = 4: timesteps 1, 251, 501, 751 (S = 3 would ask the schedule for t = 1000)
+    obj = torch.arange(N * ngen) // ngen
+    ce = synth.gaussian_like("shape_comp:e2e:c", (N, 1, 1280))
+    uce = synth.gaussian_like("shape_comp:e2e:uc", (N, 1, 1280))
+    xTe = synth.gaussian_like("shape_comp:e2e:xT", (N * ngen, 3, 16, 16, 16))
+    t0 = time.time()
+    with torch.no_grad():
+        z = vq(vol, forward_no_quant=True, encode_only=True)
+        ret = du.get_partial_shape(vol, xyz_dict=SHAPE_COMP_E2E_BOX, z=z)
+        with _QNoise("shape_comp:e2e") as qn:
+            samples, _ = DDIMSampler(D).sample(S=S2, batch_size=N * ngen, shape=(3, 16, 16, 16), conditioning=ce[obj],
+                                               verbose=False, x0=z[obj], mask=ret["z_mask"][obj], x_T=xTe,
+                                               unconditional_guidance_scale=3.0, unconditional_conditioning=uce[obj],
+                                               eta=0.0)
+        idx_rec = _record_vq_indices(vq)           # decode_no_quant quantises: keep the code indices for the flip accounting
+        gen = vq.decode_no_quant(samples)
+    assert len(qn.rec) == 4 and gen.shape == (N * ngen, 1, 64, 64, 64) and len(idx_rec) == 1
+    km = ret["shape_mask"][obj]
+    print(f"[shape_comp] e2e {time.time() - t0:.1f}s  mean |completed - input| over the known region "
+          f"{(gen - vol[obj]).abs()[km].mean():.5f}, over the rest {(gen - vol[obj]).abs()[~km].mean():.5f}")
+    out.update(e2e_box=np.array([SHAPE_COMP_E2E_BOX[k] for k in "xyz"], np.float64), e2e_S=np.int64(S2), e2e_steps=np.int64(4),
+               e2e_ngen=np.int64(ngen), e2e_scale=np.float32(3.0), e2e_z=z, e2e_z_mask=ret["z_mask"],
+               e2e_c_chk=_volume_chk(ce), e2e_uc_chk=_volume_chk(uce), e2e_xT_chk=_volume_chk(xTe),
+               e2e_q_chk=np.stack([_volume_chk(n) for n in qn.rec]), e2e_latents=samples, e2e_indices=idx_rec[0].reshape(-1, 16, 16, 16),
+               e2e_gen_sdf_sub=gen[:, :, ::2, ::2, ::2].contiguous(), e2e_part_chk=_volume_chk(ret["shape_part"]),
+               e2e_missing_chk=_volume_chk(ret["shape_missing"]))
+    save("shape_comp", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -1014,7 +1155,7 @@ def main():
     todo = a.only or ["schedule", "unet_small", "unet_full", "ddim_small", "ddim_full", "vq", "gcn", "e2e",
                       "unet_concat_small", "unet_concat_full", "ddim_concat_small", "gcn_concat", "e2e_concat", "box",
                       "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode", "shape_metrics",
-                      "constraints", "eval_losses"]
+                      "constraints", "eval_losses", "shape_comp"]
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name in todo:
@@ -1071,6 +1212,8 @@ def main():
                 g_constraints()
             elif name == "eval_losses":
                 g_eval_losses(tmp)
+            elif name == "shape_comp":
+                g_shape_comp(tmp)
             else:
                 raise SystemExit(f"unknown fixture {name}")
 
