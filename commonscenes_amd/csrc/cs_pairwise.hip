@@ -1,5 +1,6 @@
 // All-pairs shape-quality kernels (the layer scripts/compute_mmd_cov_1nn.py builds over the per-pair metric kernels):
 //   * cs_chamfer_pairwise     the Chamfer matrix of _pairwise_EMD_CD_ (:110-150), set A x set B, one workgroup per pair
+//   * cs_chamfer_pairlist     the same distance for a list of pairs of ONE set (eval_3dfront.py:688-699, consistency_check.py:78-80)
 //   * cs_emd_pairwise_cost    match_cost of every pair (approxmatch.cu:3-182 + matchcostkernel :184-224) with the whole
 //                             nine-level auction inside one workgroup and NO match matrix
 //   * cs_occupancy_histogram  the nearest-cell counters of entropy_of_occupancy_grid (:270-309)
@@ -106,6 +107,41 @@ __global__ __launch_bounds__(CD_T) void chamfer_pair_kernel(const float* __restr
     out[(int64_t)i * nb + j] = v;
     if (symmetric) out[(int64_t)j * nb + i] = v;
   }
+}
+
+// The Chamfer distance of a LIST of pairs of one cloud set (the diversity and consistency tables: consecutive runs of an
+// object, objects the ground truth marks "same as").  chamfer_pair_kernel's schedule with A = cloud pairs[k][0] and
+// B = cloud pairs[k][1]: the same slabs, the same summation pattern, the same final expression, so out[k] carries the bits
+// of cs_chamfer_pairwise(clouds, clouds)[i][j] whatever the list's length, the pair's place in it or m.
+__global__ __launch_bounds__(CD_T) void chamfer_pairlist_kernel(const float* __restrict__ clouds,
+                                                                const int32_t* __restrict__ pairs, float* __restrict__ out,
+                                                                int m, int p, int32_t* __restrict__ err) {
+  extern __shared__ float4 cd_smem[];
+  float4* tile = cd_smem;                                       // [CD_TILE]
+  unsigned* colmin = (unsigned*)(cd_smem + CD_TILE);            // [p]
+  float* part = (float*)(colmin + p);                           // [CD_T]
+  const int tid = threadIdx.x;
+  const int i = pairs[2 * (int64_t)blockIdx.x], j = pairs[2 * (int64_t)blockIdx.x + 1];
+  if (i < 0 || i >= m || j < 0 || j >= m) {                     // (the whole workgroup leaves, before any barrier)
+    if (tid == 0) out[blockIdx.x] = __builtin_nanf(""), atomicOr(err, 1);
+    return;
+  }
+  const float* A = clouds + (int64_t)i * p * 3;
+  const float* B = clouds + (int64_t)j * p * 3;
+  for (int e = tid; e < p; e += CD_T) colmin[e] = 0x7f800000u;  // +inf
+  float acc = 0.f;
+  int row0 = 0;
+  for (int slabs = (p + CD_T - 1) / CD_T; slabs > 0;) {
+    if (slabs >= 8) acc = cd_rows<8>(A, p, row0, B, p, tile, colmin, acc), row0 += 8 * CD_T, slabs -= 8;
+    else if (slabs >= 4) acc = cd_rows<4>(A, p, row0, B, p, tile, colmin, acc), row0 += 4 * CD_T, slabs -= 4;
+    else if (slabs >= 2) acc = cd_rows<2>(A, p, row0, B, p, tile, colmin, acc), row0 += 2 * CD_T, slabs -= 2;
+    else acc = cd_rows<1>(A, p, row0, B, p, tile, colmin, acc), row0 += CD_T, slabs -= 1;
+  }
+  const float srow = block_sum_256(acc, part);
+  float cacc = 0.f;
+  for (int e = tid; e < p; e += CD_T) cacc += __uint_as_float(colmin[e]);
+  const float scol = block_sum_256(cacc, part);
+  if (tid == 0) out[blockIdx.x] = srow / (float)p + scol / (float)p;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -303,6 +339,22 @@ extern "C" int cs_chamfer_pairwise(const float* a, const float* b, float* out, i
   }
   CS_LAUNCH(chamfer_pair_kernel, dim3(na * nb), dim3(CD_T), smem, (hipStream_t)stream, a, b, out, nb, p, q,
             symmetric ? 1 : 0);
+  CS_CHECK_LAUNCH();
+  return CS_OK;
+}
+
+extern "C" int cs_chamfer_pairlist(const float* clouds, const int32_t* pairs, float* out, int m, int p, int npairs,
+                                   int32_t* err, cs_stream_t stream) {
+  if (!clouds || !pairs || !out || !err || m <= 0 || p <= 0 || npairs <= 0 || p > CS_CHAMFER_PAIRWISE_MAX_Q)
+    return CS_EINVAL;
+  const size_t smem = CD_TILE * sizeof(float4) + (size_t)p * sizeof(unsigned) + CD_T * sizeof(float);
+  if (smem > 64 * 1024) {
+    (void)hipGetLastError();
+    hipError_t e = hipFuncSetAttribute((const void*)chamfer_pairlist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)smem);
+    if (e != hipSuccess) return (int)e;
+  }
+  CS_LAUNCH(chamfer_pairlist_kernel, dim3(npairs), dim3(CD_T), smem, (hipStream_t)stream, clouds, pairs, out, m, p, err);
   CS_CHECK_LAUNCH();
   return CS_OK;
 }

@@ -181,6 +181,8 @@ SIGNATURES = {
     "cs_chamfer_pairwise": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
     "cs_emd_pairwise_cost": (_i, [_f, _f, _f, _i, _i, _i, _i, _s]),
     "cs_occupancy_histogram": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _s]),
+    "cs_cloud_resample": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _f, _s]),
+    "cs_chamfer_pairlist": (_i, [_f, _f, _f, _i, _i, _i, _f, _s]),
     "cs_mc_blocks_per_object": (_i, [_i]),
     "cs_mc_count": (_i, [_f, _i, _i, _fl, _i, _f, _s]),
     "cs_mc_emit": (_i, [_f, _i, _i, _fl, _i, _f, _f, _f, _f, _f, _f, _fl, _fl, _s]),

@@ -1733,3 +1733,129 @@ def pair_stats(a: Tensor, b: Tensor, thr_a: Optional[float] = None, thr_b: Optio
                                    float(thr_a) if want_counts else 0.0, float(thr_b) if want_counts else 0.0,
                                    ws.data_ptr(), ws.numel() * 8, _stream()), "cs_pair_stats")
     return sums, counts
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# diversity / consistency tables (csrc/cs_diversity.hip, csrc/cs_pairwise.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+CHAMFER_PAIRLIST_MAX_P = 32768        # CS_CHAMFER_PAIRWISE_MAX_Q
+_INDEX_ERR: dict = {}
+
+
+def index_error_word(device=None) -> Tensor:
+    """The sticky int32 word (one per device) the two entries below OR bit 0 into when a kernel meets an index outside its
+    range.  The wrappers check indices on the host, so it stays 0; a caller that passes check_indices=False may read it."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    t = _INDEX_ERR.get(dev.index)
+    if t is None:
+        t = _INDEX_ERR[dev.index] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return t
+
+
+def _host_ints(v, name: str, what: str) -> Tensor:
+    """a host-side integer table as an int64 CPU tensor (lists, numpy arrays and CPU tensors of any integer type)"""
+    t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+    if t.numel() == 0 and not t.is_cuda:
+        return t.to(torch.int64)                   # (an empty list has no integer type to show)
+    if t.is_cuda or t.is_floating_point() or t.dtype == torch.bool:
+        raise L.CsError(f"{what}: {name} must be a host-side integer table")
+    return t.to(torch.int64)
+
+
+def cloud_resample(verts: Tensor, first, count, num: int, idx=None, normalize: bool = False,
+                   check_indices: bool = True) -> Tensor:
+    """cs_cloud_resample: out[i, e] = cloud_i[idx[i, e]] for the n clouds packed in verts [V, 3] (cloud i = the count[i] rows
+    from row first[i]); with `normalize`, each sampled cloud also goes through eval_3dfront.py:783-796 -- one launch.
+    first / count are host-side integer sequences (they are checked against V here, for free).  idx [n, num]: a host-side
+    integer table (range-checked here for free, uploaded once as int32), or an int32 device tensor (`check_indices` then costs
+    one read-back), or None = rows 0..num-1 of every cloud, which must then hold exactly `num` rows.  Returns [n, num, 3]."""
+    what = "cloud_resample"
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise L.CsError(f"{what}: verts must be a packed [V, 3] tensor")
+    first_h, count_h = _host_ints(first, "first", what).reshape(-1), _host_ints(count, "count", what).reshape(-1)
+    n, num, V = int(first_h.numel()), int(num), int(verts.shape[0])
+    if count_h.numel() != n:
+        raise L.CsError(f"{what}: first and count must be equally long")
+    if num < 1:
+        raise L.CsError(f"{what}: num must be at least 1")
+    if n and (int(count_h.min()) < 1 or int(first_h.min()) < 0 or int((first_h + count_h).max()) > V
+              or int(count_h.max()) > 0x7fffffff):
+        raise L.CsError(f"{what} failed: invalid argument (an empty cloud, or a cloud outside the {V} packed rows)")
+    if idx is None:
+        if n and not bool((count_h == num).all()):
+            raise L.CsError(f"{what} failed: invalid argument (without idx every cloud must hold exactly {num} rows)")
+    else:
+        if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
+            idx_h = _host_ints(idx, "idx", what)
+            if tuple(idx_h.shape) != (n, num):
+                raise L.CsError(f"{what}: idx must be [{n}, {num}], got {tuple(idx_h.shape)}")
+            if n and (int(idx_h.min()) < 0 or bool((idx_h >= count_h[:, None]).any())):
+                raise L.CsError(f"{what} failed: invalid argument (an index outside its cloud)")
+            idx = idx_h.to(torch.int32)
+        elif idx.dtype != torch.int32 or tuple(idx.shape) != (n, num):
+            raise L.CsError(f"{what}: a device idx must be int32 [{n}, {num}], got {idx.dtype} {tuple(idx.shape)}")
+    _chk(verts, "verts")
+    verts = verts.contiguous()
+    dev = verts.device
+    if isinstance(idx, torch.Tensor) and not idx.is_cuda:
+        idx = idx.to(dev)
+    elif idx is not None:
+        idx = idx.contiguous()
+        if idx.device != dev:
+            raise L.CsError(f"{what}: idx and verts live on different devices")
+        if check_indices and n:
+            lim = count_h.to(torch.int32).to(dev)[:, None]
+            if bool(((idx < 0) | (idx >= lim)).any()):
+                raise L.CsError(f"{what} failed: invalid argument (an index outside its cloud)")
+    out = torch.empty((n, num, 3), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    first_d, count_d = first_h.to(dev), count_h.to(torch.int32).to(dev)
+    L.check(L.load().cs_cloud_resample(verts.data_ptr(), first_d.data_ptr(), count_d.data_ptr(), _ptr(idx), out.data_ptr(),
+                                       n, num, 1 if normalize else 0, index_error_word(dev).data_ptr(), _stream()),
+            "cs_cloud_resample")
+    return out
+
+
+def chamfer_pairlist(clouds: Tensor, pairs, check_indices: bool = True) -> Tensor:
+    """cs_chamfer_pairlist: out[k] = Chamfer distance of clouds[pairs[k, 0]] and clouds[pairs[k, 1]], clouds [m, p, 3], one
+    launch; bit-equal to shape_metrics.pairwise_cd(clouds, clouds)[i, j].  pairs [npairs, 2]: a host-side integer table
+    (range-checked here for free) or an int32 device tensor (`check_indices` then costs one read-back).  Returns [npairs]."""
+    what = "chamfer_pairlist"
+    if not isinstance(clouds, torch.Tensor) or clouds.dim() != 3 or clouds.shape[2] != 3 or clouds.shape[0] < 1 \
+            or clouds.shape[1] < 1:
+        raise L.CsError(f"{what}: clouds must be a non-empty [m, p, 3] tensor")
+    m, p = int(clouds.shape[0]), int(clouds.shape[1])
+    if p > CHAMFER_PAIRLIST_MAX_P:
+        raise L.CsError(f"{what} holds one minimum per point in LDS: at most {CHAMFER_PAIRLIST_MAX_P} points")
+    on_dev = isinstance(pairs, torch.Tensor) and pairs.is_cuda
+    if not on_dev:
+        pairs_h = _host_ints(pairs, "pairs", what)
+        if pairs_h.numel() == 0:
+            pairs_h = pairs_h.reshape(0, 2)
+        if pairs_h.dim() != 2 or pairs_h.shape[1] != 2:
+            raise L.CsError(f"{what}: pairs must be [npairs, 2], got {tuple(pairs_h.shape)}")
+        if pairs_h.numel() and (int(pairs_h.min()) < 0 or int(pairs_h.max()) >= m):
+            raise L.CsError(f"{what} failed: invalid argument (a pair outside [0, {m}))")
+    elif pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise L.CsError(f"{what}: device pairs must be int32 [npairs, 2], got {pairs.dtype} {tuple(pairs.shape)}")
+    _chk(clouds, "clouds")
+    clouds = clouds.contiguous()
+    dev = clouds.device
+    if on_dev:
+        pairs = pairs.contiguous()
+        if pairs.device != dev:
+            raise L.CsError(f"{what}: pairs and clouds live on different devices")
+        if check_indices and pairs.numel() and not _index_range_ok(pairs, m):
+            raise L.CsError(f"{what} failed: invalid argument (a pair outside [0, {m}))")
+    else:
+        pairs = pairs_h.to(torch.int32).to(dev)
+    npairs = int(pairs.shape[0])
+    out = torch.empty((npairs,), dtype=torch.float32, device=dev)
+    if npairs == 0:
+        return out
+    L.check(L.load().cs_chamfer_pairlist(clouds.data_ptr(), pairs.data_ptr(), out.data_ptr(), m, p, npairs,
+                                         index_error_word(dev).data_ptr(), _stream()), "cs_chamfer_pairlist")
+    return out

@@ -783,6 +783,38 @@ int cs_occupancy_histogram(const float* clouds, const float* grid, int32_t* idx,
                            int s, int p, int g, cs_stream_t stream);
 
 /*
+ * The diversity table of scripts/eval_3dfront.py (--evaluate_diversity, :577-762) and the Chamfer half of
+ * scripts/consistency_check.py (:68-101): resample a ragged set of vertex clouds, normalise, take the Chamfer distance of a
+ * list of pairs.  Additions to ABI 18; both entries only launch, neither synchronises.
+ *
+ * cs_cloud_resample (csrc/cs_diversity.hip): out[i][e] = cloud_i[idx[i][e]] for n clouds packed in verts [V][3] -- cloud i
+ *   is the count[i] >= 1 rows from row first[i] -- one workgroup per cloud.  idx NULL = rows 0..p-1 in order (then
+ *   count[i] == p).  With normalize != 0 the sampled cloud goes through `normalize` (eval_3dfront.py:783-796) per axis, every
+ *   operation rounded to fp32 as numpy rounds it on float32 data:
+ *     s = (-lo) - ((hi - lo) * 0.5f);  w = v + s;  m = hi + s  (= max w: adding a constant is monotone);  out = w / m
+ *   lo / hi the minimum / maximum of the SAMPLED rows (order-free, so the result depends neither on n nor on the cloud's place
+ *   in the launch), the division the correctly rounded one.  An axis of zero extent gives 0 / 0 = NaN, as numpy does.
+ *   Inputs are finite by contract: numpy's amin / amax propagate a NaN, fminf / fmaxf do not.
+ *   first / count / idx live on the device.  An index is compared with count[i] before anything is read through it: a bad one
+ *   writes a NaN row and sets bit 0 of the sticky device word *err (which the caller zeroes and reads when it wants to);
+ *   nothing is dereferenced.  first[i] and count[i] themselves are trusted: first[i] + count[i] <= V is the caller's to
+ *   hold.  Rows are 12 bytes and first[i] is arbitrary: every access is a 4-byte one, no alignment beyond float's is assumed.
+ *   CS_EINVAL for n < 0, p < 1 or a NULL pointer other than idx; n == 0 is a no-op.
+ *
+ * cs_chamfer_pairlist (csrc/cs_pairwise.hip): out[k] = the Chamfer distance of clouds[pairs[k][0]] and clouds[pairs[k][1]]
+ *   for clouds [m][p][3], one workgroup per listed pair, with the slab schedule, the summation pattern and the final
+ *   srow / p + scol / p of cs_chamfer_pairwise: out[k] is bit-equal to cs_chamfer_pairwise(clouds, clouds)[i][j] for
+ *   pairs[k] = (i, j) and does not depend on npairs, on the pair's place in the list or on m.  (i, i) gives exactly 0,
+ *   (i, j) and (j, i) the same bits.  An entry outside [0, m) writes NaN and sets bit 0 of *err.
+ *   p <= CS_CHAMFER_PAIRWISE_MAX_Q (one column minimum per point in LDS, sized as in cs_chamfer_pairwise).
+ *   CS_EINVAL for NULL pointers, m, p, npairs < 1 or p beyond the limit.
+ */
+int cs_cloud_resample(const float* verts, const int64_t* first, const int32_t* count, const int32_t* idx, float* out, int n,
+                      int p, int normalize, int32_t* err, cs_stream_t stream);
+int cs_chamfer_pairlist(const float* clouds, const int32_t* pairs, float* out, int m, int p, int npairs, int32_t* err,
+                        cs_stream_t stream);
+
+/*
  * SDF -> triangle mesh by marching cubes (model/diff_utils/util_3d.py:194-236 sdf_to_mesh, which runs
  * PyMCubes' mcubes.marching_cubes(sdf_i, level) on the CPU per object).  sdf: [nb][n][n][n] fp32 (the decoder's
  * (B,1,64,64,64) output as is), n <= 160.  A vertex per grid edge whose endpoints straddle `level` ((v < level) differs),

@@ -190,7 +190,13 @@ def main():
     ap.add_argument("--constraints", action="store_true",
                     help="additionally evaluate every scene's sampled boxes against its graph (constraints.validate_constrains: "
                          "scripts/eval_3dfront.py:722 -> helpers/metrics_3dfront.py:57-179) and report the accuracy table")
+    ap.add_argument("--diversity-gpu", action="store_true",
+                    help="additionally feed every scene's diversity runs to commonscenes_amd.diversity.DiversityMeter (the "
+                         "reference's figures: denormalised boxes, circular angle deviation, per-category table; resampling, "
+                         "normalisation and all Chamfer pairs on the device) and report its summary as `diversity`")
     a = ap.parse_args()
+    if a.diversity_gpu and a.samples < 2:
+        ap.error("--diversity-gpu needs at least two runs per object (--samples)")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     one = os.environ.get("CS_ONE_DEVICE") == "1"
@@ -285,6 +291,12 @@ def main():
         if a.constraints:
             from commonscenes_amd import constraints as CN
             accuracy, mapped = CN.new_accuracy(), 0
+        if a.diversity_gpu:
+            from commonscenes_amd.diversity import CATEGORIES, DiversityMeter
+            # the synthetic vocabulary read as SG-FRONT's: class 0 `_scene_`, the last class `floor`, the ten categories 1..10
+            meter = DiversityMeter({"_scene_": 0, "floor": 34, **{n: i for i, n in enumerate(CATEGORIES, start=1)}},
+                                   points=a.points)
+            meter_gen = torch.Generator().manual_seed(48)      # its own generator: the keys below draw what they always drew
         x_T = None                                            # like the reference: fresh noise per call
         all_div_boxes, all_div_angles, all_div_chamfer = [], [], []
         t_all = time.perf_counter()
@@ -310,16 +322,22 @@ def main():
                 if a.export_scenes and rank == 0 else None
             # --evaluate_diversity
             boxes_div, angle_div, shapes_sample = [], [], []
+            div_angles, div_sdfs = [], []
             for _ in range(a.samples):
                 with torch.no_grad():
                     dboxes, dsdf = model.sample_box_and_shape(None, dec_objs, dec_triples, dec_sdfs, text, rel,
                                                               attributes=None, gen_shape=True, ddim_steps=a.ddim_steps)
                 pts = sample_points(sdf_to_mesh(dsdf, render_all=True).verts_list(), a.points)
                 dboxes, dangles = dboxes
+                div_angles.append(dangles)
+                div_sdfs.append(dsdf)
                 norm = [torch.from_numpy(normalize(p.cpu().numpy())).cuda() for p in pts]
                 boxes_div.append(dboxes)
                 angle_div.append(np.expand_dims(np.argmax(dangles.cpu().numpy(), 1), 1) / 24.0 * 360.0)
                 shapes_sample.append(torch.stack(norm))
+            if a.diversity_gpu:
+                shaped = torch.unique(torch.where(torch.ne(dec_sdfs, torch.zeros_like(dec_sdfs[0])))[0]).tolist()
+                meter.add_scene(dec_objs, boxes_div, div_angles, div_sdfs, shape_nodes=shaped, generator=meter_gen)
             bd = torch.stack(boxes_div, 1)
             all_div_boxes += torch.std(bd, dim=1).cpu().numpy().tolist()
             all_div_angles += np.stack(angle_div, 1).std(axis=1).reshape(-1).tolist()
@@ -341,6 +359,8 @@ def main():
         res.update(total_s=time.perf_counter() - t_all, box_std_mean=float(np.mean(all_div_boxes)),
                    angle_std_mean=float(np.mean(all_div_angles)), chamfer_diversity_mean=float(np.mean(all_div_chamfer)),
                    chamfer_diversity_n=len(all_div_chamfer))
+        if a.diversity_gpu:
+            res["diversity"] = meter.summary()
         if a.constraints:
             res["accuracy"] = dict({k: dict(satisfied=int(sum(v)), evaluated=len(v)) for k, v in accuracy.items()},
                                    mapped_triples=mapped)

@@ -1146,6 +1146,107 @@ def g_shape_comp(tmp: Path):
     save("shape_comp", **out)
 
 
+DIVERSITY_COUNTS = (1, 3, 17, 64, 65, 257, 3000)
+DIVERSITY_NUMS = (64, 257)
+
+
+def _ref_normalize():
+    """`normalize` of scripts/eval_3dfront.py:783-796.  The module parses its arguments at import, so only that function's AST
+    node is compiled, here and now; nothing of it is kept."""
+    import ast
+    path = REF / "scripts" / "eval_3dfront.py"
+    tree = ast.parse(path.read_text())
+    node = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "normalize")
+    ns = {"np": np}
+    exec(compile(ast.Module(body=[node], type_ignores=[]), str(path), "exec"), ns)
+    return ns["normalize"]
+
+
+class _RecordDraws:
+    """torch.randperm / torch.randint wrapped for one call of the reference's sample_points: every draw is kept"""
+
+    def __enter__(self):
+        self.rec, self._perm, self._int = [], torch.randperm, torch.randint
+
+        def randperm(*a, **k):
+            r = self._perm(*a, **k)
+            self.rec.append(("randperm", r.clone()))
+            return r
+
+        def randint(*a, **k):
+            r = self._int(*a, **k)
+            self.rec.append(("randint", r.clone()))
+            return r
+        torch.randperm, torch.randint = randperm, randint
+        return self
+
+    def __exit__(self, *exc):
+        torch.randperm, torch.randint = self._perm, self._int
+        return False
+
+
+def g_diversity():
+    """tests/golden/diversity.npz: what the reference's own functions give on the CPU for the pieces of the diversity table --
+    helpers.util.sample_points (with the rows it drew), scripts/eval_3dfront.py's normalize, helpers.metrics_3dfront's
+    estimate_angular_std and torch.std(batch_torch_denormalize_box_params(...), dim=1)."""
+    import helpers.metrics_3dfront as M
+    import helpers.util as U
+    normalize = _ref_normalize()
+    out = {"counts": np.array(DIVERSITY_COUNTS, np.int64), "nums": np.array(DIVERSITY_NUMS, np.int64)}
+    rng = np.random.default_rng(2024)
+    clouds = [torch.from_numpy((rng.random((n, 3)) * np.array([1.0, 0.6, 0.3]) - np.array([0.5, 0.1, 0.0])).astype(np.float32))
+              for n in DIVERSITY_COUNTS]
+    out["verts"] = torch.cat(clouds)
+    for num in DIVERSITY_NUMS:
+        torch.manual_seed(47)
+        with _RecordDraws() as rec:
+            got = U.sample_points(clouds, num)
+        assert len(rec.rec) == len(clouds)
+        kinds = [k for k, _ in rec.rec]
+        assert kinds == ["randperm" if n >= num else "randint" for n in DIVERSITY_COUNTS], kinds
+        idx = torch.stack([r[:num] for _, r in rec.rec])
+        smp = torch.stack(got)
+        assert all(torch.equal(c[i], s) for c, i, s in zip(clouds, idx, smp))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            nrm = np.stack([normalize(s.numpy().copy()) for s in smp])
+        assert nrm.dtype == np.float32
+        out[f"idx_{num}"], out[f"sampled_{num}"], out[f"normalized_{num}"] = idx.to(torch.int32), smp, nrm
+        print(f"[diversity] num {num}: NaN entries {int(np.isnan(nrm).sum())} (the one-vertex cloud's)")
+    # three hand-made clouds: one point, a zero-extent axis, coordinates around 1e3
+    hand = [np.array([[0.25, -0.5, 0.125]], np.float32),
+            np.stack([np.linspace(-0.3, 0.4, 9), np.full(9, 0.2), np.linspace(1.0, 0.0, 9) ** 2], 1).astype(np.float32),
+            (1e3 + 3.0 * rng.random((33, 3))).astype(np.float32)]
+    for i, h in enumerate(hand):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[f"hand_{i}"], out[f"hand_normalized_{i}"] = h, normalize(h.copy())
+        assert out[f"hand_normalized_{i}"].dtype == np.float32
+    # estimate_angular_std on the 15-degree grid: [O = 6, K] sets, some straddling 0 / 360, one all equal
+    for K in (2, 3, 5):
+        degs = (rng.integers(0, 24, (6, K)) * 15.0).astype(np.float64)
+        degs[1] = np.resize(np.array([345.0, 0.0, 15.0, 330.0, 30.0]), K)        # straddles 0 / 360
+        degs[2] = np.resize(np.array([0.0, 345.0]), K)
+        degs[3] = 165.0                                                             # all equal
+        degs[4] = np.resize(np.array([180.0, 195.0, 165.0]), K)                     # around 180: no wrap
+        out[f"angles_{K}"] = degs
+        out[f"angular_std_{K}"] = np.array([M.estimate_angular_std(list(d)) for d in degs], np.float64)
+        print(f"[diversity] K {K}: estimate_angular_std {out[f'angular_std_{K}'].round(6).tolist()} "
+              f"(plain std {degs.std(axis=1).round(3).tolist()})")
+    # torch.std(batch_torch_denormalize_box_params(...), dim=1), without and with a statistics file
+    boxes = torch.from_numpy(rng.normal(0.0, 1.0, (6, 3, 6)).astype(np.float32))
+    stats = np.stack([rng.normal(0.5, 1.0, 8), rng.uniform(0.5, 2.0, 8)])
+    out["boxes"], out["box_stats"] = boxes, stats
+    with tempfile.TemporaryDirectory() as td:
+        f = str(Path(td) / "stats.txt")
+        np.savetxt(f, stats)
+        out["box_stats"] = np.loadtxt(f)
+        for tag, file in (("none", None), ("file", f)):
+            den = U.batch_torch_denormalize_box_params(boxes.reshape([-1, 6]), file=file).reshape([6, -1, 6])
+            out[f"box_den_absmax_{tag}"] = den.abs().reshape(-1, 6).max(dim=0).values.double()
+            out[f"box_std_{tag}"] = torch.std(den, dim=1)
+            print(f"[diversity] box std ({tag}): dtype {out[f'box_std_{tag}'].dtype}")
+    save("diversity", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -1155,7 +1256,7 @@ def main():
     todo = a.only or ["schedule", "unet_small", "unet_full", "ddim_small", "ddim_full", "vq", "gcn", "e2e",
                       "unet_concat_small", "unet_concat_full", "ddim_concat_small", "gcn_concat", "e2e_concat", "box",
                       "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode", "shape_metrics",
-                      "constraints", "eval_losses", "shape_comp"]
+                      "constraints", "eval_losses", "shape_comp", "diversity"]
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name in todo:
@@ -1214,6 +1315,8 @@ def main():
                 g_eval_losses(tmp)
             elif name == "shape_comp":
                 g_shape_comp(tmp)
+            elif name == "diversity":
+                g_diversity()
             else:
                 raise SystemExit(f"unknown fixture {name}")
 
