@@ -17,16 +17,13 @@
 // WHOLE wave (the owner's set-up is broadcast with shuffles, the 64 lanes stride the bounding box).  The key image makes the
 // result independent of which path, wave or launch order drew a pixel.
 #include "cs_common.h"
+#include "cs_raster.h"
 
 namespace {
 
 constexpr int FIT_THREADS = 1024;
 constexpr int APPLY_THREADS = 256;
 constexpr int APPLY_BLOCKS = 32;       // workgroups per object (grid-stride inside the object)
-constexpr int RASTER_THREADS = 256;
-constexpr int RASTER_OWN_PIXELS = 8;
-constexpr int SUB = 256;               // sub-pixel grid: vertices snap to 1/256 pixel
-constexpr float SNAP_LIMIT = 2097152.f;   // |pixel coordinate| clamp (2^21): edge functions stay below 2^62 in int64
 
 __global__ __launch_bounds__(FIT_THREADS) void scene_fit_kernel(const float* __restrict__ verts, int64_t total_verts,
                                                                 const int64_t* __restrict__ vert_base,
@@ -151,28 +148,6 @@ __global__ __launch_bounds__(APPLY_THREADS) void scene_apply_kernel(
   }
 }
 
-struct Tri {
-  int x[3], y[3];          // snapped to 1/256 pixel; after set-up the winding has positive area
-  float d[3];              // depth 8 - y of the three vertices
-  int x0, x1, y0, y1;      // clamped pixel bounding box, inclusive; x1 < x0: nothing to draw
-  int64_t area;            // twice the signed area in (1/256 pixel)^2, > 0
-};
-
-__device__ __forceinline__ int snap(float pix) {
-  pix = fminf(fmaxf(pix, -SNAP_LIMIT), SNAP_LIMIT);
-  return (int)floorf(pix * (float)SUB + 0.5f);
-}
-
-__device__ __forceinline__ int64_t edge_fn(int ax, int ay, int bx, int by, int px, int py) {
-  return (int64_t)(bx - ax) * (int64_t)(py - ay) - (int64_t)(by - ay) * (int64_t)(px - ax);
-}
-
-// top-left rule for the positive winding of edge_fn (x right, y down): a top edge runs right, a left edge runs up
-__device__ __forceinline__ bool top_left(int ax, int ay, int bx, int by) {
-  const int dx = bx - ax, dy = by - ay;
-  return (dy == 0 && dx > 0) || dy < 0;
-}
-
 // returns 0 drawable, 1 dropped (a vertex nearer than znear, or not finite), 2 nothing to draw
 __device__ int tri_setup(const float* __restrict__ verts, int64_t nverts, const int64_t* __restrict__ faces, int64_t f,
                          int size, float znear, Tri& t) {
@@ -192,55 +167,7 @@ __device__ int tri_setup(const float* __restrict__ verts, int64_t nverts, const 
     t.y[i] = snap((1.0f + z / d) * 0.5f * (float)size);
   }
   if (behind) return 1;
-  int64_t area = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], t.x[2], t.y[2]);
-  if (area == 0) return 2;
-  if (area < 0) {                                             // both faces are drawn: make the winding positive
-    int ti = t.x[1]; t.x[1] = t.x[2]; t.x[2] = ti;
-    ti = t.y[1]; t.y[1] = t.y[2]; t.y[2] = ti;
-    float tf = t.d[1]; t.d[1] = t.d[2]; t.d[2] = tf;
-    area = -area;
-  }
-  t.area = area;
-  const int xmin = min(t.x[0], min(t.x[1], t.x[2])), xmax = max(t.x[0], max(t.x[1], t.x[2]));
-  const int ymin = min(t.y[0], min(t.y[1], t.y[2])), ymax = max(t.y[0], max(t.y[1], t.y[2]));
-  // pixel p's centre sits at p * 256 + 128: first centre >= min, last centre <= max (arithmetic shifts floor)
-  t.x0 = max((xmin - SUB / 2 + SUB - 1) >> 8, 0);
-  t.x1 = min((xmax - SUB / 2) >> 8, size - 1);
-  t.y0 = max((ymin - SUB / 2 + SUB - 1) >> 8, 0);
-  t.y1 = min((ymax - SUB / 2) >> 8, size - 1);
-  if (t.x1 < t.x0 || t.y1 < t.y0) {
-    t.x1 = t.x0 - 1;
-    return 2;
-  }
-  return 0;
-}
-
-__device__ __forceinline__ void tri_pixel(const Tri& t, uint32_t face, int px, int py, int size,
-                                          unsigned long long* __restrict__ keys) {
-  const int cx = px * SUB + SUB / 2, cy = py * SUB + SUB / 2;
-  const int64_t e0 = edge_fn(t.x[1], t.y[1], t.x[2], t.y[2], cx, cy);     // weight of vertex 0
-  const int64_t e1 = edge_fn(t.x[2], t.y[2], t.x[0], t.y[0], cx, cy);
-  const int64_t e2 = edge_fn(t.x[0], t.y[0], t.x[1], t.y[1], cx, cy);
-  const bool in = (e0 > 0 || (e0 == 0 && top_left(t.x[1], t.y[1], t.x[2], t.y[2]))) &&
-                  (e1 > 0 || (e1 == 0 && top_left(t.x[2], t.y[2], t.x[0], t.y[0]))) &&
-                  (e2 > 0 || (e2 == 0 && top_left(t.x[0], t.y[0], t.x[1], t.y[1])));
-  if (!in) return;
-  float d = t.d[0];                 // a triangle parallel to the image plane has that depth exactly (so coplanar ones tie)
-  if (t.d[0] != t.d[1] || t.d[1] != t.d[2]) {
-    const float a = (float)t.area;
-    const float inv = (((float)e0 / a) / t.d[0] + ((float)e1 / a) / t.d[1]) + ((float)e2 / a) / t.d[2];
-    d = 1.0f / inv;                 // perspective-correct depth, > 0: its bits order like uints
-  }
-  const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | face;
-  unsigned long long* k = keys + (int64_t)py * size + px;
-  // keys only ever fall, so a (possibly stale) value already below ours means the atomic would change nothing
-  if (__hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= key) return;
-  atomicMin(k, key);
-}
-
-__device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
-  const int lo = __shfl((int)(v & 0xffffffff), src, 64), hi = __shfl((int)(v >> 32), src, 64);
-  return ((int64_t)hi << 32) | (uint32_t)lo;
+  return tri_finish(t, size);
 }
 
 __global__ __launch_bounds__(RASTER_THREADS) void scene_raster_kernel(const float* __restrict__ verts, int64_t nverts,
@@ -257,33 +184,10 @@ __global__ __launch_bounds__(RASTER_THREADS) void scene_raster_kernel(const floa
     const int64_t f = f0 + lane;
     Tri t;
     int st = 2;
-    t.x0 = 0, t.x1 = -1, t.y0 = 0, t.y1 = -1, t.area = 1;
-    for (int i = 0; i < 3; ++i) t.x[i] = t.y[i] = 0, t.d[i] = 1.f;
+    tri_clear(t);
     if (f < nfaces) st = tri_setup(verts, nverts, faces, f, size, znear, t);
     ndrop += st == 1;
-    const int64_t npix = st == 0 ? (int64_t)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) : 0;
-    if (npix > 0 && npix <= RASTER_OWN_PIXELS) {
-      for (int py = t.y0; py <= t.y1; ++py)
-        for (int px = t.x0; px <= t.x1; ++px) tri_pixel(t, (uint32_t)f, px, py, size, keys);
-    }
-    unsigned long long big = __ballot(npix > RASTER_OWN_PIXELS);
-    while (big) {
-      const int src = __ffsll((long long)big) - 1;
-      big &= big - 1;
-      Tri s;
-      for (int i = 0; i < 3; ++i) {
-        s.x[i] = __shfl(t.x[i], src, 64);
-        s.y[i] = __shfl(t.y[i], src, 64);
-        s.d[i] = __shfl(t.d[i], src, 64);
-      }
-      s.x0 = __shfl(t.x0, src, 64), s.x1 = __shfl(t.x1, src, 64);
-      s.y0 = __shfl(t.y0, src, 64), s.y1 = __shfl(t.y1, src, 64);
-      s.area = shfl64(t.area, src);
-      const int w = s.x1 - s.x0 + 1;
-      const int64_t n = (int64_t)w * (s.y1 - s.y0 + 1);
-      for (int64_t p = lane; p < n; p += 64)
-        tri_pixel(s, (uint32_t)(f0 + src), s.x0 + (int)(p % w), s.y0 + (int)(p / w), size, keys);
-    }
+    tri_draw_wave(t, st, f0, lane, size, keys);
   }
   for (int o = 32; o > 0; o >>= 1) ndrop += __shfl_xor(ndrop, o, 64);
   if (lane == 0 && ndrop) atomicAdd(dropped, ndrop);

@@ -231,6 +231,12 @@ SIGNATURES = {
     "cs_q_sample": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _l, _l, _i, _l, _l, _s]),
     "cs_pair_stats": (_i, [_f, _f, _i, _l, _l, _l, _f, _f, _fl, _fl, _f, _l, _s]),
     "cs_ddim_masked_blend": (_i, [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _l, _i, _l, _i, _i, _l, _l, _s]),
+    "cs_view_normalize": (_i, [_f, _l, _f, _f, _i, _f, _f, _s]),
+    "cs_view_project": (_i, [_f, _l, _f, _f, _i, _i, C.POINTER(C.c_float), _fl, _i, _f, _f, _f, _f, _s]),
+    "cs_view_vertex_normals": (_i, [_f, _l, _f, _l, _f, _f, _f, _f, _i, _f, _f, _f, _s]),
+    "cs_view_raster": (_i, [_f, _f, _l, _f, _l, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _s]),
+    "cs_view_shade": (_i, [_f, _f, _f, _f, _f, _f, _l, _f, _l, _f, _f, _f, _f, _i, _i, C.POINTER(C.c_float), _f, _f, _f, _f,
+                           _s]),
     "cs_abi_version": (_i, []),
 }
 

@@ -859,6 +859,26 @@ class SDFusionText2ShapeModel:
         self.switch_eval()
         return self._sample_all(self.rel[:num_obj], self.uc_rel[:num_obj], ddim_steps, ddim_eta, uc_scale, x_T, max_steps)
 
+    @property
+    def renderer(self):
+        """sdfusion_txt2shape_model.py:110-112: init_mesh_renderer(image_size=256, dist=1.7, elev=20, azim=20), on first use"""
+        if getattr(self, "_renderer", None) is None:
+            from .object_views import init_mesh_renderer
+            self._renderer = init_mesh_renderer(image_size=256, dist=1.7, elev=20, azim=20, device="cuda")
+        return self._renderer
+
+    @torch.no_grad()
+    def get_current_visuals(self, vocab, obj_ids, num_obj=2):
+        """:645-668: OrderedDict(img_gt, img_gen_df) of uint8 grids: the first num_obj input SDFs and the generated ones,
+        rendered by object_views.  The reference's third panel, img_text (the object names drawn with cv2.putText), is not
+        built: cv2 is not part of this package's image.  self.text_obj still holds the names."""
+        from collections import OrderedDict
+        from .object_views import render_sdf, tensor2im
+        self.text_obj = [vocab.get(i) for i in obj_ids[:num_obj]]
+        self.img_gt = render_sdf(self.renderer, self.x[:num_obj]).detach().cpu()
+        self.img_gen_df = render_sdf(self.renderer, self.gen_df).detach().cpu()
+        return OrderedDict((name, tensor2im(getattr(self, name))) for name in ("img_gt", "img_gen_df"))
+
     # ---- checkpoint surface (VAEGAN_V2FULL.py:687-699 stores these under 'df' / 'vqvae') ----
     def state_dict(self):
         return {"df": self.df.state_dict(), "vqvae": self.vqvae.state_dict()}

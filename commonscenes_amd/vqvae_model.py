@@ -2,10 +2,12 @@
 
   iou(x_gt, x, thres)        model/diff_utils/util.py:111-130 -- one cs_pair_stats launch instead of two mask volumes
   VQLoss(codebook_weight)    model/losses.py:63-83, forward value and log dict (no autograd graph)
-  VQVAEModel                 set_input / forward / inference / test_iou / eval_metrics (vqvae_model.py:97-168)
+  VQVAEModel                 set_input / forward / inference / test_iou / eval_metrics / get_current_visuals
+                             (vqvae_model.py:97-168, 204-218); the views come from object_views (256^2, camera 1.7, 20, 20,
+                             vqvae_model.py:70-71)
 
-Not built: the renderer (`should_render`, get_current_visuals), `best_iou` / `save`, the optimiser and everything that
-needs a backward pass (`backward`, `optimize_parameters`): they raise NotImplementedError.
+Not built: `best_iou` / `save`, the optimiser and everything that needs a backward pass (`backward`,
+`optimize_parameters`): they raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -119,12 +121,32 @@ class VQVAEModel:
     @torch.no_grad()
     def inference(self, data, should_render=False, verbose=False):
         """:110-124: encode without quantising, then decode_no_quant (which quantises to the nearest code first)."""
-        if should_render:
-            raise NotImplementedError("the renderer is not built")
         self.switch_eval()
         self.set_input(data)
         self.z = self.vqvae(self.x, forward_no_quant=True, encode_only=True)
         self.x_recon = self.vqvae_module.decode_no_quant(self.z)
+        if should_render:
+            self._render()
+
+    @property
+    def renderer(self):
+        """:70-71: init_mesh_renderer(image_size=256, dist=1.7, elev=20, azim=20), built on first use"""
+        if getattr(self, "_renderer", None) is None:
+            from .object_views import init_mesh_renderer
+            self._renderer = init_mesh_renderer(image_size=256, dist=1.7, elev=20, azim=20, device=self.device)
+        return self._renderer
+
+    def _render(self):
+        from .object_views import render_sdf
+        self.image = render_sdf(self.renderer, self.x)
+        self.image_recon = render_sdf(self.renderer, self.x_recon)
+
+    @torch.no_grad()
+    def get_current_visuals(self):
+        """:204-218: OrderedDict(image, image_recon) of uint8 grids (tensor2im) of the last input and its reconstruction"""
+        from .object_views import tensor2im
+        self._render()
+        return OrderedDict((name, tensor2im(getattr(self, name))) for name in ("image", "image_recon"))
 
     @torch.no_grad()
     def test_iou(self, data, thres=0.0):

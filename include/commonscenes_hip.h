@@ -1086,6 +1086,64 @@ int cs_ddim_masked_blend(const float* x0, const float* noise, const float* mask,
                          int64_t rows, int channels, int64_t inner, int mask_channels, int T, int64_t x0_rows,
                          int64_t mask_rows, cs_stream_t stream);
 
+/*
+ * Per-object views (csrc/cs_view.hip): the reference's object renderer, model/diff_utils/util_3d.py:135-189 init_mesh_renderer
+ * and :350-393 render_sdf / render_meshes over pytorch3d's MeshRasterizer + HardPhongShader, with helpers/util.py:242-258
+ * normalize_py3d_meshes in front.  pytorch3d is not part of the build image: its conventions are restated here from its
+ * documented behaviour, and parity with it is NOT pinned.  Every buffer is caller-owned device memory unless said otherwise;
+ * nothing synchronises.
+ *
+ * The batch: n meshes (1..65535) packed in verts [total_verts][3] fp32, faces [total_faces][3] int64 holding PACKED vertex
+ * ids, vert_rgb [total_verts][3] fp32; mesh i owns vert_count[i] vertices from vert_base[i] and face_count[i] faces from
+ * face_base[i] ([n] int64, device), as in cs_scene_apply.  A range that leaves its buffer makes the mesh empty; a face with an
+ * id outside its own mesh's vertex range is never dereferenced and draws nothing.  Rows no mesh owns are neither read nor
+ * written.
+ *
+ * cs_view_normalize: centre [3] fp32 (out) = the mean over the vertices of ALL meshes (fp64 sums folded in a fixed order:
+ *   deterministic), out_verts = (v - centre) / r_i with r_i = max |v - centre| over mesh i (fp32).  r_i == 0 or a non-finite
+ *   vertex: that mesh collapses to the origin (the reference would produce NaN) and later draws nothing.
+ * cs_view_project: [normalize != 0: cs_view_normalize into `world` first; else world = verts] then per vertex
+ *   view = cam12 . (p, 1), cam12 = row-major 3x4 [R^T | T] of pytorch3d's look_at_view_transform (12 HOST floats; the host
+ *   builds it in fp64), each row ((m0 x + m1 y) + m2 z) + m3 in fp32;  ndc = focal * (x_view, y_view) / z_view
+ *   (focal = 1 / tan(fov / 2)), +X left, +Y up;  pixel (row i, col j) has its centre at ndc (1 - (2j+1)/size,
+ *   1 - (2i+1)/size), so the pixel coordinate is (1 - ndc) * size / 2.  -> screen [total_verts][2] int32 = (col, row)
+ *   snapped to 1/256 pixel like cs_scene_raster_topdown, zview [total_verts] fp32 (NaN for a non-finite vertex; screen is
+ *   (0, 0) when z_view <= 0).  `world` must not alias `verts`.
+ * cs_view_vertex_normals: pytorch3d verts_normals_packed: every face adds (v1 - v0) x (v2 - v0) (fp64) to its three vertices,
+ *   the sum is normalised with eps 1e-6.  Sums are taken in 64-bit fixed point (accum [total_verts][3] int64, workspace), so
+ *   the result is bit-reproducible and independent of the face order; the power-of-two scale comes from each mesh's bounding
+ *   box (mesh_scale [n] fp32, workspace/out; 0 = a point or a non-finite vertex: zero normals) and leaves room for 2^22
+ *   faces around one vertex.
+ * cs_view_raster: keys [n][size][size] uint64 (reset by the call), one image per mesh, the rasteriser of
+ *   cs_scene_raster_topdown (exact integer coverage on the snapped grid, top-left rule, both windings, perspective-correct fp32
+ *   depth, key = depth bits << 32 | PACKED face id, atomic min).  A triangle with a vertex at z_view < zmin or not finite is
+ *   dropped whole (no clipping) and counted in dropped [n] int32 (reset by the call).
+ * cs_view_shade: per pixel: the winning face's integer edge functions again, perspective-correct barycentrics
+ *   w_i ~ (e_i / area) / z_i renormalised, interpolated vertex colour, vertex normal and world position, then HardPhongShader
+ *   with pytorch3d's default PointLights / Materials: light (0, 1, 0), ambient 0.5, diffuse 0.3, specular 0.2, shininess 64;
+ *   n = norm(n), l = norm(L - p), r = -l + 2 (n.l) n, v = norm(eye - p), rgb = (0.5 + 0.3 max(n.l, 0)) texel +
+ *   0.2 (max(v.r, 0) [n.l > 0])^64; no clamp, no two-sided lighting.  eye3: the camera position, 3 HOST floats.
+ *   -> image [n][size][size][4] fp32 (background 1, 1, 1, alpha 0; covered alpha 1), pix_to_face [n][size][size] int64
+ *   (packed face id, -1 empty), zbuf fp32 (-1 empty), bary [n][size][size][3] fp32 (0 where empty).
+ */
+int cs_view_normalize(const float* verts, int64_t total_verts, const int64_t* vert_base, const int64_t* vert_count, int n,
+                      float* centre, float* out_verts, cs_stream_t stream);
+int cs_view_project(const float* verts, int64_t total_verts, const int64_t* vert_base, const int64_t* vert_count, int n,
+                    int normalize, const float* cam12, float focal, int size, float* centre, float* world, int32_t* screen,
+                    float* zview, cs_stream_t stream);
+int cs_view_vertex_normals(const float* verts, int64_t total_verts, const int64_t* faces, int64_t total_faces,
+                           const int64_t* vert_base, const int64_t* vert_count, const int64_t* face_base,
+                           const int64_t* face_count, int n, int64_t* accum, float* mesh_scale, float* normals,
+                           cs_stream_t stream);
+int cs_view_raster(const int32_t* screen, const float* zview, int64_t total_verts, const int64_t* faces, int64_t total_faces,
+                   const int64_t* vert_base, const int64_t* vert_count, const int64_t* face_base, const int64_t* face_count,
+                   int n, int size, float zmin, uint64_t* keys, int32_t* dropped, cs_stream_t stream);
+int cs_view_shade(const uint64_t* keys, const float* world, const float* normals, const float* vert_rgb,
+                  const int32_t* screen, const float* zview, int64_t total_verts, const int64_t* faces, int64_t total_faces,
+                  const int64_t* vert_base, const int64_t* vert_count, const int64_t* face_base, const int64_t* face_count,
+                  int n, int size, const float* eye3, float* image, int64_t* pix_to_face, float* zbuf, float* bary,
+                  cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

@@ -161,6 +161,25 @@ def export_scene(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs):
                 covered=int((img["object_id"] >= 0).sum()), apply_bytes=36 * nv + 52 * nf, **times)
 
 
+def export_object_views(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs, renderer):
+    """--object-views: one normalised 256x256 RGBA view per shaped object -- the raw, inverted, coloured meshes of
+    get_generated_models_v2 through helpers/visualize_scene.py:42-55 get_current_visuals_v2 and :29-40 store_current_imgs
+    -> DIR/render_object_imgs/<scan>/<label>_<cat>_<instance>.png"""
+    from commonscenes_amd import object_views as OV, scene_mesh as S
+    img_dir = Path(out_dir) / "render_object_imgs" / str(scan)
+    img_dir.mkdir(parents=True, exist_ok=True)
+    classes = list(VOCAB["object_idx_to_name"])
+    classes[0], classes[-1] = "_scene_\n", "floor\n"
+    cats = dec_objs.cpu().tolist()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    raw = S.get_generated_models_v2(torch.cat([boxes_pred.float(), angles_pred.float()], dim=1), meshes, cats, classes)[2]
+    visuals = OV.get_current_visuals_v2(VOCAB, renderer, raw, cats)
+    t1 = time.perf_counter()
+    paths = OV.store_current_imgs(visuals, str(img_dir), classes, cats)
+    return len(paths), t1 - t0, time.perf_counter() - t1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=2)
@@ -187,6 +206,10 @@ def main():
                          "hands to trimesh.Scene, helpers/visualize_scene.py:401-436) and render its 256x256 top-down view "
                          "(render_img, :85-116); writes DIR/<scan>.obj and DIR/<scan>.png (.npy without PIL) and reports the "
                          "device time next to a host numpy restatement of the fit (helpers/util.py:158-189)")
+    ap.add_argument("--object-views", action="store_true",
+                    help="with --export-scenes DIR: additionally render every shaped object on its own (object_views: the "
+                         "reference's init_mesh_renderer(256, 1.7, 20, 20) + get_current_visuals_v2) and write "
+                         "DIR/render_object_imgs/<scan>/<label>_<cat>_<instance>.png; reports the image count and time")
     ap.add_argument("--constraints", action="store_true",
                     help="additionally evaluate every scene's sampled boxes against its graph (constraints.validate_constrains: "
                          "scripts/eval_3dfront.py:722 -> helpers/metrics_3dfront.py:57-179) and report the accuracy table")
@@ -195,6 +218,8 @@ def main():
                          "reference's figures: denormalised boxes, circular angle deviation, per-category table; resampling, "
                          "normalisation and all Chamfer pairs on the device) and report its summary as `diversity`")
     a = ap.parse_args()
+    if a.object_views and not a.export_scenes:
+        ap.error("--object-views needs --export-scenes DIR")
     if a.diversity_gpu and a.samples < 2:
         ap.error("--diversity-gpu needs at least two runs per object (--samples)")
 
@@ -297,6 +322,10 @@ def main():
             meter = DiversityMeter({"_scene_": 0, "floor": 34, **{n: i for i, n in enumerate(CATEGORIES, start=1)}},
                                    points=a.points)
             meter_gen = torch.Generator().manual_seed(48)      # its own generator: the keys below draw what they always drew
+        if a.object_views:
+            from commonscenes_amd.object_views import init_mesh_renderer
+            view_renderer = init_mesh_renderer(image_size=256, dist=1.7, elev=20, azim=20, device="cuda")   # eval_3dfront.py:476-478
+            views = dict(images=0, render_s=0.0, write_s=0.0)
         x_T = None                                            # like the reference: fresh noise per call
         all_div_boxes, all_div_angles, all_div_chamfer = [], [], []
         t_all = time.perf_counter()
@@ -320,6 +349,11 @@ def main():
             nshape = shapes_pred.shape[0]
             export = export_scene(a.export_scenes, data["scan_id"][0], meshes, boxes_pred, angles_pred, dec_objs) \
                 if a.export_scenes and rank == 0 else None
+            if a.object_views and rank == 0:
+                n_img, t_r, t_w = export_object_views(a.export_scenes, data["scan_id"][0], meshes, boxes_pred, angles_pred,
+                                                       dec_objs, view_renderer)
+                views = dict(images=views["images"] + n_img, render_s=views["render_s"] + t_r,
+                             write_s=views["write_s"] + t_w)
             # --evaluate_diversity
             boxes_div, angle_div, shapes_sample = [], [], []
             div_angles, div_sdfs = [], []
@@ -359,6 +393,8 @@ def main():
         res.update(total_s=time.perf_counter() - t_all, box_std_mean=float(np.mean(all_div_boxes)),
                    angle_std_mean=float(np.mean(all_div_angles)), chamfer_diversity_mean=float(np.mean(all_div_chamfer)),
                    chamfer_diversity_n=len(all_div_chamfer))
+        if a.object_views:
+            res["object_views"] = views
         if a.diversity_gpu:
             res["diversity"] = meter.summary()
         if a.constraints:
