@@ -16,6 +16,7 @@
 #include <atomic>
 #include <cstring>
 #include "cs_f16x3.h"
+#include "cs_epilogue.h"
 
 namespace {
 
@@ -206,12 +207,7 @@ __global__ __launch_bounds__(256) void conv_gemm_f32_kernel(const CsConvGemm p, 
         const int row = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
         const int m = m0 + row;
         if (nok && m < M) {
-          float v = acc[i][j][r] + bias;
-          if (p.scale) v = v * sc + sh;
-          if (p.rowvec) v += p.rowvec[(int64_t)(m / p.rv_rows) * p.ldrv + n];
-          v = cs_act(v, p.act);
-          if (p.res) v += p.res[(int64_t)m * p.ldr + n];
-          p.out[(int64_t)m * p.ldo + n] = v;
+          p.out[(int64_t)m * p.ldo + n] = cs_epi_terms1(p, acc[i][j][r], bias, sc, sh, m, n);
         }
       }
     }
@@ -350,8 +346,8 @@ int plan_splitk(const CsConvGemm& p, int64_t M) {
   return s < 1 ? 1 : (int)s;
 }
 
-// sums the split-K partial tiles in slice order and applies the epilogue of conv_gemm_* (bias, BN scale/shift,
-// row vector, activation, residual); one float4 of one output row per thread
+// sums the split-K partial tiles in slice order and applies the epilogue terms (cs_epilogue.h::cs_epi_terms4: bias, BN
+// scale/shift, row vector, activation, residual); one float4 of one output row per thread
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const CsConvGemm p, const float* __restrict__ ws, int M,
                                                             int splits) {
   const int n4 = p.cout >> 2;
@@ -361,15 +357,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const CsConvGemm p, 
     const int n = (int)(i - (int64_t)m * n4) * 4;
     f32x4 v = *reinterpret_cast<const f32x4*>(ws + (int64_t)m * p.cout + n);
     for (int s = 1; s < splits; ++s) v += *reinterpret_cast<const f32x4*>(ws + ((int64_t)s * M + m) * p.cout + n);
-    if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-    if (p.scale) v = v * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
-    if (p.rowvec) v += *reinterpret_cast<const f32x4*>(p.rowvec + (int64_t)(m / p.rv_rows) * p.ldrv + n);
-    if (p.act != CS_ACT_NONE) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = cs_act(v[e], p.act);
-    }
-    if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (int64_t)m * p.ldr + n);
-    *reinterpret_cast<f32x4*>(p.out + (int64_t)m * p.ldo + n) = v;
+    *reinterpret_cast<f32x4*>(p.out + (int64_t)m * p.ldo + n) = cs_epi_terms4(p, v, m, n);
   }
 }
 
@@ -378,13 +366,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const CsConvGemm p, 
 // workgroups, 16 instead of 9.5 us per call at one object) -- so that it can (a) leave the fp64 (sum, sum of
 // squares) of its rows per column for the GroupNorm that follows (statistics tile = SKR rows; at small batches nearly
 // every GroupNorm input comes out of this kernel) and (b) write the interleaved operand pair, lanes 2t / 2t + 1 swapping a
-// half as in the GEMM's own epilogue.  Same sums, same order per element as splitk_reduce_kernel.
+// half.  Slice-order sums as in splitk_reduce_kernel; terms, pair and column sums are cs_epilogue.h's.
 constexpr int SKR = 16;
 __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const CsConvGemm p, const float* __restrict__ ws, int M,
                                                                 int splits) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   __shared__ double sc[16][64];
   const int cbn = (p.cout + 63) / 64;
   const int rb = blockIdx.x / cbn, cbi = blockIdx.x - rb * cbn;
@@ -402,14 +387,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const CsConvGemm
     if (ok) {
       v = *reinterpret_cast<const f32x4*>(ws + (int64_t)m * p.cout + n);
       for (int sl = 1; sl < splits; ++sl) v += *reinterpret_cast<const f32x4*>(ws + ((int64_t)sl * M + m) * p.cout + n);
-      if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-      if (p.scale) v = v * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
-      if (p.rowvec) v += *reinterpret_cast<const f32x4*>(p.rowvec + (int64_t)(m / p.rv_rows) * p.ldrv + n);
-      if (p.act != CS_ACT_NONE) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = cs_act(v[e], p.act);
-      }
-      if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (int64_t)m * p.ldr + n);
+      v = cs_epi_terms4(p, v, m, n);
       if (gstat) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -420,57 +398,23 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const CsConvGemm
       }
     }
     if (opair) {      // uniform branch: every lane takes part in the half swap
-      h4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float o = v[e] * p.out_scale;
-        oamax = fmaxf(oamax, fabsf(o));
-        hi[e] = (_Float16)o;
-        lo[e] = (_Float16)(o - (float)hi[e]);
-      }
-      const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
-      const bool odd = cl & 1;
-      const u32x2 send = odd ? H : L;
-      u32x2 recv;
-      recv[0] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[0], 0xB1, 0xF, 0xF, true);
-      recv[1] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[1], 0xB1, 0xF, 0xF, true);
-      u32x4 r;
-      r[0] = odd ? recv[0] : H[0];
-      r[1] = odd ? recv[1] : H[1];
-      r[2] = odd ? L[0] : recv[0];
-      r[3] = odd ? L[1] : recv[1];
-      if (ok) {
-        char* row = reinterpret_cast<char*>(p.out + (int64_t)m * p.ldo);
-        *reinterpret_cast<u32x4*>(row + (n >> 4) * 64 + ((n & 8) ? 32 : 0) + ((n & 4) ? 16 : 0)) = r;
-      }
+      const cs_u32x4 r = cs_pair16(v, p.out_scale, cl & 1, oamax);
+      if (ok) *reinterpret_cast<cs_u32x4*>(reinterpret_cast<char*>(p.out + (int64_t)m * p.ldo) + cs_pair_off(n)) = r;
     } else if (ok) {
       *reinterpret_cast<f32x4*>(p.out + (int64_t)m * p.ldo + n) = v;
     }
   }
-  if (opair && p.status && oamax >= 65504.f) atomicOr(p.status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_flag(p, opair, oamax);
   if (gstat) {
-    double tot[2][4];
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sc[rl][cl * 4 + e] = which ? q[e] : s[e];
-      __syncthreads();
-      if (rl == 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          double t = 0.0;
-          for (int r2 = 0; r2 < 16; ++r2) t += sc[r2][cl * 4 + e];
-          tot[which][e] = t;
-        }
-      }
-    }
+    double ts[4], tq[4];
+    cs_colsum_lanes16(sc, s, rl, cl, ts);
+    cs_colsum_lanes16(sc, q, rl, cl, tq);
     if (rl == 0 && nok) {
       double* o = p.gn_part + ((int64_t)rb * p.gn_ld + n) * 2;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        o[2 * e] = tot[0][e];
-        o[2 * e + 1] = tot[1][e];
+        o[2 * e] = ts[e];
+        o[2 * e + 1] = tq[e];
       }
     }
   }
@@ -485,9 +429,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const CsConvGemm
 template <int R>
 __global__ __launch_bounds__(256) void wino_out_kernel(const CsConvGemm p, const float* __restrict__ ws, int M, int splits,
                                                        int tail_unit0, int tail_splits, int unit_cols) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   constexpr int P = R + 2;
   __shared__ double sc[16][64];
   const int cbn = (p.cout + 63) / 64;
@@ -544,14 +485,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(const CsConvGemm p, const
     const int64_t m = t * R + e;
     f32x4 v = y[e];
     if (tok) {
-      if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-      if (p.scale) v = v * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
-      if (p.rowvec) v += *reinterpret_cast<const f32x4*>(p.rowvec + (m / p.rv_rows) * p.ldrv + n);
-      if (p.act != CS_ACT_NONE) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = cs_act(v[k], p.act);
-      }
-      if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + m * p.ldr + n);
+      v = cs_epi_terms4(p, v, m, n);
       if (gstat) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -564,57 +498,23 @@ __global__ __launch_bounds__(256) void wino_out_kernel(const CsConvGemm p, const
       v = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (opair) {      // uniform branch: every lane takes part in the half swap
-      h4 hi, lo;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float o = v[k] * p.out_scale;
-        oamax = fmaxf(oamax, fabsf(o));
-        hi[k] = (_Float16)o;
-        lo[k] = (_Float16)(o - (float)hi[k]);
-      }
-      const u32x2 H = __builtin_bit_cast(u32x2, hi), Lw = __builtin_bit_cast(u32x2, lo);
-      const bool odd = cl & 1;
-      const u32x2 send = odd ? H : Lw;
-      u32x2 recv;
-      recv[0] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[0], 0xB1, 0xF, 0xF, true);
-      recv[1] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[1], 0xB1, 0xF, 0xF, true);
-      u32x4 r;
-      r[0] = odd ? recv[0] : H[0];
-      r[1] = odd ? recv[1] : H[1];
-      r[2] = odd ? Lw[0] : recv[0];
-      r[3] = odd ? Lw[1] : recv[1];
-      if (tok) {
-        char* row = reinterpret_cast<char*>(p.out + m * p.ldo);
-        *reinterpret_cast<u32x4*>(row + (n >> 4) * 64 + ((n & 8) ? 32 : 0) + ((n & 4) ? 16 : 0)) = r;
-      }
+      const cs_u32x4 r = cs_pair16(v, p.out_scale, cl & 1, oamax);
+      if (tok) *reinterpret_cast<cs_u32x4*>(reinterpret_cast<char*>(p.out + m * p.ldo) + cs_pair_off(n)) = r;
     } else if (tok) {
       *reinterpret_cast<f32x4*>(p.out + m * p.ldo + n) = v;
     }
   }
-  if (opair && p.status && oamax >= 65504.f) atomicOr(p.status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_flag(p, opair, oamax);
   if (gstat) {
-    double tot[2][4];
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 4; ++k) sc[tl][cl * 4 + k] = which ? sq[k] : s[k];
-      __syncthreads();
-      if (tl == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          double a = 0.0;
-          for (int r2 = 0; r2 < 16; ++r2) a += sc[r2][cl * 4 + k];
-          tot[which][k] = a;
-        }
-      }
-    }
+    double ts[4], tq[4];
+    cs_colsum_lanes16(sc, s, tl, cl, ts);
+    cs_colsum_lanes16(sc, sq, tl, cl, tq);
     if (tl == 0 && nok) {
       double* o = p.gn_part + ((int64_t)rb * p.gn_ld + n) * 2;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        o[2 * k] = tot[0][k];
-        o[2 * k + 1] = tot[1][k];
+      for (int e = 0; e < 4; ++e) {
+        o[2 * e] = ts[e];
+        o[2 * e + 1] = tq[e];
       }
     }
   }
@@ -1340,7 +1240,8 @@ __global__ __launch_bounds__(256) void up2_interleave_kernel(const float* __rest
 
 // r5: the K-sliced class batch of small launches (cs_conv_gemm_up2): ws [cls][slice][M1][cout] partial tiles -> the sum over
 // the slices IN SLICE ORDER + bias + activation, stored to the class's rows of the doubled grid.  One launch instead of a
-// reduce per class and the interleave pass; per element the arithmetic of splitk_reduce_kernel.
+// reduce per class and the interleave pass; per element the slice-order sum of splitk_reduce_kernel and the bias / activation
+// terms of cs_epilogue.h::cs_epi_terms4 (no descriptor here: written out).
 __global__ __launch_bounds__(256) void up2_reduce_scatter_kernel(const float* __restrict__ ws, const float* __restrict__ bias,
                                                                  float* __restrict__ out, int64_t m1, int cout, int ldo,
                                                                  int D, int H, int W, int ud, int uh, int uw, int splits,

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "cs_f16x3.h"
+#include "cs_epilogue.h"
 #include <type_traits>
 #include <utility>
 
@@ -86,9 +87,11 @@ struct CsClsBatch {
 
 // The slices of output tile `otile` have each stored their partial tile to ws[slice][M][cout].  Publish, arrive, and -- the
 // LAST R ARRIVERS only (r6) -- wait for the rest, then sum rows [share * BM/R, +BM/R) of the tile over the slices IN SLICE
-// ORDER and apply the epilogue: per element the arithmetic of splitk_reduce_epi_kernel / splitk_reduce_kernel (cs_gemm.hip),
-// per (16-row block, column) the same fp64 row-order sums for gn_part, the same pair conversion -- bit for bit the two-kernel
-// form whichever workgroup ends up with which share.
+// ORDER (as splitk_reduce_epi_kernel / splitk_reduce_kernel, cs_gemm.hip, do) and apply the epilogue: per element the terms of
+// cs_epilogue.h (cs_epi_terms4); the pair conversion and the fp64 row-order sums per (16-row block, column) for gn_part are
+// the expressions of that header's cs_pair16 / cs_colsum_staged WRITTEN OUT here (calling them grew the SGPR spill counts of a dozen
+// instantiations of the tile kernel this routine is inlined into) -- bit for bit the two-kernel form whichever workgroup ends
+// up with which share.
 // Visibility (MI355X_MICROARCH.md "inter-workgroup visibility", the write-through form): the partial tile goes out as 16-byte
 // `sc1` stores -> `s_waitcnt vmcnt(0)` (inline asm) -> barrier -> one lane's relaxed agent-scope atomic on the tile's counter;
 // the reducers poll that counter with relaxed agent-scope loads and read the partials with `sc1` loads (never served by a
@@ -163,14 +166,7 @@ __device__ __forceinline__ void fused_splitk_reduce(const CsFuseK& f, const floa
           for (int q = 0; q < 8; ++q)
             if (s + q < splits) v += t[q];
         }
-        if (f.bias) v += *reinterpret_cast<const f32x4*>(f.bias + n);
-        if (f.scale) v = v * *reinterpret_cast<const f32x4*>(f.scale + n) + *reinterpret_cast<const f32x4*>(f.shift + n);
-        if (f.rowvec) v += *reinterpret_cast<const f32x4*>(f.rowvec + (int64_t)(m / f.rv_rows) * f.ldrv + n);
-        if (f.act != CS_ACT_NONE) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = cs_act(v[e], f.act);
-        }
-        if (f.res) v += *reinterpret_cast<const f32x4*>(f.res + (int64_t)m * f.ldr + n);
+        v = cs_epi_terms4(f, v, m, n);
       }
       if (gstat && u < UNITS) *reinterpret_cast<f32x4*>(lv + lrow * BN + 4 * c4) = v;     // (masked rows / columns: zeros)
       if (opair) {                                           // uniform branch: every lane takes part in the half swap
@@ -218,7 +214,7 @@ __device__ __forceinline__ void fused_splitk_reduce(const CsFuseK& f, const floa
       __syncthreads();
     }
   }
-  if (opair && f.status && oamax >= 65504.f) atomicOr(f.status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_flag(f, opair, oamax);
   // leave: the last reducer of the tile returns both counters to zero (every reducer has left its wait by then; the slices
   // that do not reduce arrived before that wait could end)
   __syncthreads();
@@ -965,7 +961,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
   // combined and stored.  Stores are buffer stores whose inactive lanes carry an out-of-range offset, so every pass
   // issues exactly KU of them and the counted vmcnt below is exact.  The fused GEGLU gate takes the same route.
   {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    typedef cs_u32x4 u32x4;
     constexpr int QR = 2;                                    // accumulator registers per pass -> 4 rows per wave
     constexpr int NQ = 16 / QR;
     constexpr int UPR = WCOLS / 4;                           // float4 units per row
@@ -1017,34 +1013,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
 #pragma unroll
         for (int e = 0; e < 2; ++e) gs[k][e] = gq[k][e] = f32x2{0.f, 0.f};
       float oamax = 0.f;                                     // largest |out * out_scale| this lane converted (opair)
-      // interleaved pair: lanes 2t / 2t + 1 hold columns 8g .. 8g+3 / 8g+4 .. 8g+7 of one row (UPR is even); the even lane
-      // stores [hi 8g .. 8g+7], the odd one [lo 8g .. 8g+7] -- one 16-byte store each after swapping a half (quad_perm 1,0,3,2)
-      auto pair16 = [&](const f32x4& v) -> u32x4 {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        h4 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float o = v[e] * p.out_scale;
-          oamax = fmaxf(oamax, fabsf(o));
-          hi[e] = (_Float16)o;
-          lo[e] = (_Float16)(o - (float)hi[e]);
-        }
-        const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
-        const bool odd = lane & 1;
-        const u32x2 send = odd ? H : L;
-        u32x2 recv;
-        recv[0] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[0], 0xB1, 0xF, 0xF, true);
-        recv[1] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[1], 0xB1, 0xF, 0xF, true);
-        u32x4 r;
-        r[0] = odd ? recv[0] : H[0];
-        r[1] = odd ? recv[1] : H[1];
-        r[2] = odd ? L[0] : recv[0];
-        r[3] = odd ? L[1] : recv[1];
-        return r;
-      };
-      // byte offset of that store inside the row: 64-byte chunks of 16 columns = [hi 0-7 | lo 0-7 | hi 8-15 | lo 8-15]
-      auto pair_off = [](int col) -> unsigned { return (unsigned)((col >> 4) * 64 + ((col & 8) ? 32 : 0) + ((col & 4) ? 16 : 0)); };
+      // (interleaved pair, cs_epilogue.h::cs_pair16: UPR is even, so lanes 2t / 2t + 1 hold columns 8g .. / 8g+4 .. of one row)
       float* const rs = reinterpret_cast<float*>(smem + RES0 + wave * 2 * RSLAB);
       float* const vb = reinterpret_cast<float*>(smem + VEC0);
       float* const vr = vb + 256;
@@ -1125,13 +1094,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
                 xv += *reinterpret_cast<const f32x4*>(vb + wn0 + 4 * c4);
                 gv += *reinterpret_cast<const f32x4*>(vb + wn0 + HC + 4 * c4);
               }
-#pragma unroll
-              for (int e = 0; e < 4; ++e) xv[e] = xv[e] * ((CS_ABLATE & 32768) ? gv[e] : cs_gelu(gv[e]));
+              xv = (CS_ABLATE & 32768) ? xv * gv : cs_geglu4(xv, gv);
               off = (unsigned)(orel(row) * p.ldo + (n0 + wn0) / 2 + 4 * c4) * 4u;
             }
             if (opair) {                                     // (uniform branch: every lane takes part in the half swap)
-              const u32x4 pk = pair16(xv);
-              if (ok) off = (unsigned)(orel(row) * p.ldo) * 4u + pair_off((n0 + wn0) / 2 + 4 * c4);
+              const u32x4 pk = cs_pair16(xv, p.out_scale, lane & 1, oamax);
+              if (ok) off = (unsigned)(orel(row) * p.ldo) * 4u + (unsigned)cs_pair_off((n0 + wn0) / 2 + 4 * c4);
               if (CS_ABLATE & 16384) off = OOB;
               __builtin_amdgcn_raw_buffer_store_b128(pk, ors, off, 0, 0);
             } else {
@@ -1168,8 +1136,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
           }
           if (CS_ABLATE & 16384) off = OOB;
           if (opair) {
-            const u32x4 pk = pair16(v);
-            if (ok && !(CS_ABLATE & 16384)) off = (unsigned)(orel(row) * p.ldo) * 4u + pair_off(n0 + wn0 + 4 * c4);
+            const u32x4 pk = cs_pair16(v, p.out_scale, lane & 1, oamax);
+            if (ok && !(CS_ABLATE & 16384)) off = (unsigned)(orel(row) * p.ldo) * 4u + (unsigned)cs_pair_off(n0 + wn0 + 4 * c4);
             __builtin_amdgcn_raw_buffer_store_b128(pk, ors, off, 0, 0);
           } else {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, off, 0, 0);   // OOB lanes: dropped
@@ -1189,7 +1157,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
       all_q(std::integral_constant<int, 0>{});
       if constexpr (WMB > 1) all_q(std::integral_constant<int, 1>{});
       static_assert(WMB <= 2 && NQ == 8, "pass enumeration");
-      if (opair && p.status && oamax >= 65504.f) atomicOr(p.status, CS_STATUS_F16X3_OVERFLOW);
+      cs_pair_flag(p, opair, oamax);
       if (gstat) {
         // lanes -> [wave][staged row][column] in LDS, then thread t < BN adds column t over the waves that own it and
         // the four staged rows, always in the same order; the tile's (sum, sum of squares) row goes out as 16-byte pairs
@@ -1273,9 +1241,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
                   xv += *reinterpret_cast<const f32x4*>(p.bias + n);
                   gv += *reinterpret_cast<const f32x4*>(p.bias + n + HC);
                 }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) xv[e] = xv[e] * cs_gelu(gv[e]);
-                *reinterpret_cast<f32x4*>(outp + (ob + orel(m - m0)) * p.ldo + (n0 + wn0) / 2 + 4 * c4) = xv;
+                *reinterpret_cast<f32x4*>(outp + (ob + orel(m - m0)) * p.ldo + (n0 + wn0) / 2 + 4 * c4) = cs_geglu4(xv, gv);
               }
             }
           }
@@ -1291,16 +1257,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
             const int m = m0 + wm0 + 32 * i + EPI_ROWS * ph + lrow;
             const int n = n0 + wn0 + 4 * c4;
             if (m < M) {
-              f32x4 v = *reinterpret_cast<const f32x4*>(ep + lrow * WCOLS + 4 * c4);
-              if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-              if (p.scale)
-                v = v * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
-              if (p.rowvec) v += *reinterpret_cast<const f32x4*>(p.rowvec + (int64_t)(m / p.rv_rows) * p.ldrv + n);
-              if (p.act != CS_ACT_NONE) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = cs_act(v[e], p.act);
-              }
-              if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (int64_t)m * p.ldr + n);
+              const f32x4 v = cs_epi_terms4(p, *reinterpret_cast<const f32x4*>(ep + lrow * WCOLS + 4 * c4), m, n);
               if (fz.sync)        // (uniform) a K slice of a fused-reduce launch: write-through, see fused_splitk_reduce
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, v), prs,
                                                        (unsigned)(((m - m0) * p.ldo + n) * 4), 0, 16);
@@ -1333,12 +1290,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         const int row = wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
         const int m = m0 + row;
         if (nok && m < M) {
-          float v = acc[i][j][r] * acc_scale_ + bias;
-          if (p.scale) v = v * sc + sh;
-          if (p.rowvec) v += p.rowvec[(int64_t)(m / p.rv_rows) * p.ldrv + n];
-          v = cs_act(v, p.act);
-          if (p.res) v += p.res[(int64_t)m * p.ldr + n];
-          outp[(ob + orel(row)) * p.ldo + n] = v;
+          outp[(ob + orel(row)) * p.ldo + n] = cs_epi_terms1(p, acc[i][j][r] * acc_scale_, bias, sc, sh, m, n);
         }
       }
     }

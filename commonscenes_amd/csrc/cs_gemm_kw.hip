@@ -19,6 +19,7 @@
 #include <cstring>
 #include <type_traits>
 #include "cs_f16x3.h"
+#include "cs_epilogue.h"
 
 namespace {
 
@@ -193,9 +194,6 @@ __global__ __launch_bounds__(256, 1) void kw_gemm_f16x3_kernel(const CsConvGemm 
   __syncthreads();
 
   // ---- one epilogue over the tile: thread = (row, float4 column), four units each ----
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   const bool gstat = p.gn_part != nullptr, opair = p.out_format == 2;
   float* const fin = reinterpret_cast<float*>(smem + 16384);    // [64][64] final values (gn_part): wave 0's ring, upper half
   float oamax = 0.f;
@@ -211,61 +209,23 @@ __global__ __launch_bounds__(256, 1) void kw_gemm_f16x3_kernel(const CsConvGemm 
     v += *reinterpret_cast<const f32x4*>(smem + 3 * KW_WAVE + (row * 64 + 4 * c4) * 4);
     v = v * acc_scale;
     if (ok) {
-      if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-      if (p.scale) v = v * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
-      if (p.rowvec) v += *reinterpret_cast<const f32x4*>(p.rowvec + (int64_t)(m / p.rv_rows) * p.ldrv + n);
-      if (p.act != CS_ACT_NONE) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = cs_act(v[e], p.act);
-      }
-      if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + (int64_t)m * p.ldr + n);
+      v = cs_epi_terms4(p, v, m, n);
     } else {
       v = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (gstat) *reinterpret_cast<f32x4*>(fin + row * 64 + 4 * c4) = v;
     if (opair) {                                                // uniform branch: every lane takes part in the half swap
-      h4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float o = v[e] * p.out_scale;
-        oamax = fmaxf(oamax, fabsf(o));
-        hi[e] = (_Float16)o;
-        lo[e] = (_Float16)(o - (float)hi[e]);
-      }
-      const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
-      const bool odd = tid & 1;
-      const u32x2 send = odd ? H : L;
-      u32x2 recv;
-      recv[0] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[0], 0xB1, 0xF, 0xF, true);
-      recv[1] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[1], 0xB1, 0xF, 0xF, true);
-      u32x4 r;
-      r[0] = odd ? recv[0] : H[0];
-      r[1] = odd ? recv[1] : H[1];
-      r[2] = odd ? L[0] : recv[0];
-      r[3] = odd ? L[1] : recv[1];
-      if (ok) {
-        char* orow = reinterpret_cast<char*>(p.out + (int64_t)m * p.ldo);
-        *reinterpret_cast<u32x4*>(orow + (n >> 4) * 64 + ((n & 8) ? 32 : 0) + ((n & 4) ? 16 : 0)) = r;
-      }
+      const cs_u32x4 r = cs_pair16(v, p.out_scale, tid & 1, oamax);
+      if (ok) *reinterpret_cast<cs_u32x4*>(reinterpret_cast<char*>(p.out + (int64_t)m * p.ldo) + cs_pair_off(n)) = r;
     } else if (ok) {
       *reinterpret_cast<f32x4*>(p.out + (int64_t)m * p.ldo + n) = v;
     }
   }
-  if (opair && p.status && oamax >= 65504.f) atomicOr(p.status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_flag(p, opair, oamax);
   if (gstat) {
     // per (64-row statistics tile, column): the fp64 sum and sum of squares of the FINAL values, rows in order
     __syncthreads();
-    if (tid < 64 && n0 + tid < p.cout) {
-      double ts = 0.0, tq = 0.0;
-      for (int r2 = 0; r2 < 64; ++r2) {
-        const double d = (double)fin[r2 * 64 + tid];
-        ts += d;
-        tq += d * d;
-      }
-      double* o = p.gn_part + ((int64_t)tm * p.gn_ld + n0 + tid) * 2;
-      o[0] = ts;
-      o[1] = tq;
-    }
+    if (tid < 64 && n0 + tid < p.cout) cs_colsum_staged(p, fin + tid, 64, 64, tm, n0 + tid);
   }
 }
 

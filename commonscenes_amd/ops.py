@@ -567,6 +567,28 @@ def _epilogue_extras(lib, p, x_dev, nb: int, rps: int, m_tiles_rows: int, cout: 
     return st, took
 
 
+def _set_epilogue_terms(p, w: PackedWeight, mo: int, act, rowvec, rv_rows, res, scale, shift) -> None:
+    """The epilogue terms of a conv / GEMM descriptor with `mo` output rows: the weight's bias, BN scale / shift, the
+    activation, and the validated row-vector and residual views."""
+    p.bias = _ptr(w.bias)
+    p.scale, p.shift = _ptr(scale), _ptr(shift)
+    p.rowvec, p.res = _ptr(rowvec), _ptr(res)
+    p.act, p.rv_rows = act, rv_rows
+    p.ldr = p.ldrv = 0
+    if res is not None:
+        _chk(res, "res")
+        rm, rc, ldr = rows_ld(res, "res")
+        if rm != mo or rc != w.cout:
+            raise L.CsError("res shape mismatch")
+        p.ldr = ldr
+    if rowvec is not None:
+        _chk(rowvec, "rowvec")
+        vm, vc, ldrv = rows_ld(rowvec, "rowvec")
+        if vc != w.cout or vm * rv_rows < mo:
+            raise L.CsError("rowvec shape mismatch")
+        p.ldrv = ldrv
+
+
 def conv_gemm(x: Tensor, w: PackedWeight, *, spatial: Optional[Tuple[int, int, int, int]] = None,
               stride: Sequence[int] = (1, 1, 1), up: Sequence[int] = (0, 0, 0), act: int = L.ACT_NONE,
               rowvec: Optional[Tensor] = None, rv_rows: int = 1, res: Optional[Tensor] = None,
@@ -684,33 +706,16 @@ def conv_gemm(x: Tensor, w: PackedWeight, *, spatial: Optional[Tuple[int, int, i
         p.status = status_word(x.device).data_ptr()
     else:
         p.x, p.w, p.out = x.data_ptr(), w.wt.data_ptr(), out.data_ptr()
-    p.bias = _ptr(w.bias)
-    p.scale, p.shift = _ptr(scale), _ptr(shift)
-    p.rowvec = _ptr(rowvec)
-    p.res = _ptr(res)
     p.nb, p.din, p.hin, p.win = nb, d, h, wd
     p.dout, p.hout, p.wout = do, ho, wo
     p.cin, p.cout = w.cin_pad, w.cout
     p.lda, p.ldw, p.ldo = lda, w.ldw, ldo
-    p.ldr = 0
-    if res is not None:
-        _chk(res, "res")
-        rm, rc, ldr = rows_ld(res, "res")
-        if rm != mo or rc != w.cout:
-            raise L.CsError("res shape mismatch")
-        p.ldr = ldr
-    p.ldrv = 0
-    if rowvec is not None:
-        _chk(rowvec, "rowvec")
-        vm, vc, ldrv = rows_ld(rowvec, "rowvec")
-        if vc != w.cout or vm * rv_rows < mo:
-            raise L.CsError("rowvec shape mismatch")
-        p.ldrv = ldrv
+    _set_epilogue_terms(p, w, mo, act, rowvec, rv_rows, res, scale, shift)
     p.kd, p.kh, p.kw = kd, kh, kw
     p.sd, p.sh, p.sw = stride
     p.pd, p.ph, p.pw = pd, ph, pw
     p.ud, p.uh, p.uw = up
-    p.act, p.rv_rows, p.math, p.tile = act, rv_rows, math, tile
+    p.math, p.tile = math, tile
     if x_bound is not None and math == L.MATH_F16X3 and xs is None and xp is None and _sw("DYN_SCALE"):
         p.a_bound = x_bound.data_ptr()
     lib = L.load()
@@ -780,23 +785,7 @@ def _conv_wino(xw: "Wino16", w: PackedWeight, act, rowvec, rv_rows, res, scale, 
     p.a_scale = float(xw.a_scale)
     p.acc_scale = wacc * (A_SCALE / float(xw.a_scale))
     p.status = status_word(dev).data_ptr()
-    p.bias = _ptr(w.bias)
-    p.scale, p.shift = _ptr(scale), _ptr(shift)
-    p.rowvec = _ptr(rowvec)
-    p.res = _ptr(res)
-    p.act, p.rv_rows = act, rv_rows
-    if res is not None:
-        _chk(res, "res")
-        rm, rc, ldr = rows_ld(res, "res")
-        if rm != mo or rc != w.cout:
-            raise L.CsError("res shape mismatch")
-        p.ldr = ldr
-    if rowvec is not None:
-        _chk(rowvec, "rowvec")
-        vm, vc, ldrv = rows_ld(rowvec, "rowvec")
-        if vc != w.cout or vm * rv_rows < mo:
-            raise L.CsError("rowvec shape mismatch")
-        p.ldrv = ldrv
+    _set_epilogue_terms(p, w, mo, act, rowvec, rv_rows, res, scale, shift)
     sk, wsb = C.c_int32(1), C.c_int64(0)
     L.check(lib.cs_conv_wino_plan(C.byref(p), C.byref(sk), C.byref(wsb)), "cs_conv_wino_plan")
     ws = torch.empty((wsb.value // 4,), dtype=torch.float32, device=dev)
