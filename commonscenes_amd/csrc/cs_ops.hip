@@ -510,6 +510,9 @@ extern "C" int cs_ddim_coefficients(float a_t, float a_prev, float sigma_t, floa
   return CS_OK;
 }
 
+// max that keeps a NaN (fmaxf returns its non-NaN operand and would drop a NaN of the tensor before the clamp of absmax_slot_kernel)
+__device__ __forceinline__ float absmax_keep_nan(float m, float a) { return (a > m || a != a) ? a : m; }
+
 // max |x| of an fp32 tensor folded into *slot by atomicMax of the bits (non-negative floats order like their bit patterns):
 // zero the slot first.  r6: the UNet's conv_in reads the RAW latent x_t, whose magnitude no normalisation bounds -- both hosts
 // leave its exact max |.| in a bound slot (CsConvGemm.a_bound) so that the F16X3 operand scale follows it instead of the
@@ -518,13 +521,13 @@ __global__ __launch_bounds__(256) void absmax_slot_kernel(const float* __restric
   __shared__ float red[4];
   float m = 0.f;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf(x[i]));
+    m = absmax_keep_nan(m, fabsf(x[i]));
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  for (int o = 32; o > 0; o >>= 1) m = absmax_keep_nan(m, __shfl_xor(m, o));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    m = absmax_keep_nan(absmax_keep_nan(red[0], red[1]), absmax_keep_nan(red[2], red[3]));
     if (!(m < 3.0e38f)) m = 3.0e38f;                 // inf / NaN: a bound no scale can honour -- the kernel's flag reports it
     atomicMax(reinterpret_cast<unsigned int*>(slot), __float_as_uint(m));
   }
