@@ -573,3 +573,78 @@ class Sg2ScVAEModel(BoxVAEMixin):
             gens = self.Diff.rel2shape_many(datas, ddim_steps=ddim_steps, uc_scale=3., x_Ts=x_Ts, launch_B=launch_B)
         return [(self.decoder(z, objs, triples, text, rel, attributes), gens[i])
                 for i, (z, objs, triples, text, rel, attributes) in enumerate(prepared)]
+
+    # ---- several manipulation decodes through one coalesced sampler ----
+    @staticmethod
+    def _entry(e, *names, default=None, required=True):
+        for n in names:
+            if n in e:
+                return e[n]
+        if required:
+            raise KeyError(f"manipulation entry lacks {' / '.join(names)}")
+        return default
+
+    def _manipulation_many(self, entries, changes: bool, gen_shape, ddim_steps, launch_B, shape_nodes):
+        """decoder_with_changes (changes=True) / decoder_with_additions over a list of entries.  Entry i's latent is built
+        first -- its host draws (_insert_nodes' multivariate_normal, then the np.random.normal rows of the changed nodes in
+        node order) complete before entry i + 1's and before any sampling, so one np.random.seed gives the latents of the
+        per-scene method called entry after entry.  Each entry's graph runs through the GCNs on its own (the same launches
+        as the per-scene call: the same bits); the shaped objects of ALL entries go through one Diff.rel2shape_many."""
+        if shape_nodes not in ("all", "changed"):
+            raise ValueError(f"shape_nodes must be 'all' or 'changed', got {shape_nodes!r}")
+        dev = self.device
+        prepared, datas, x_Ts, picked = [], [], [], []
+        for e in entries:
+            z = self._entry(e, "z", "z_box")
+            objs, triples = self._entry(e, "dec_objs", "objs"), self._entry(e, "dec_triples", "triples")
+            text = self._entry(e, "encoded_dec_text_feat").to(device=dev, dtype=torch.float32)
+            rel = self._entry(e, "encoded_dec_rel_feat").to(device=dev, dtype=torch.float32)
+            attributes = e.get("attributes")
+            missing, manipulated = list(e["missing_nodes"]), list(e["manipulated_nodes"])
+            distribution = e.get("distribution")
+            if changes:
+                z, nodes_added = self._changed_latent(z, objs, triples, text, rel, attributes, missing, manipulated,
+                                                      distribution)
+            else:
+                z, nodes_added = self._insert_nodes(z, missing, distribution, z.shape[1])
+            changed = sorted(set(nodes_added) | set(int(m) for m in manipulated))
+            prepared.append((z, objs, triples, text, rel, attributes, nodes_added, manipulated))
+            if gen_shape:
+                un_rel_feat, rel_feat = self.encoder_2(z, objs, triples, text, rel, attributes)
+                dec_sdfs = self._entry(e, "dec_sdfs")
+                mask = torch.ne(dec_sdfs, torch.zeros_like(dec_sdfs[0]))
+                ids = torch.unique(torch.where(mask)[0])
+                if shape_nodes == "changed":                    # keep == 0 and a non-zero dec_sdfs row, in node order
+                    ids = ids[torch.isin(ids, torch.tensor(changed, dtype=torch.int64))] if changed else ids[:0]
+                ids_d = ids.to(dev)
+                datas.append({"sdf": dec_sdfs[ids], "rel": rel_feat[ids_d], "uc": un_rel_feat[ids_d]})
+                x_Ts.append(e.get("x_T"))
+                picked.append(ids)
+        gens = [None] * len(entries)
+        if gen_shape and entries:
+            gens = self.Diff.rel2shape_many(datas, ddim_steps=ddim_steps, uc_scale=3., x_Ts=x_Ts, launch_B=launch_B)
+            if shape_nodes == "changed":
+                gens = [(g, ids.tolist()) for g, ids in zip(gens, picked)]
+        out = []
+        for i, (z, objs, triples, text, rel, attributes, nodes_added, manipulated) in enumerate(prepared):
+            pred = self.decoder(z, objs, triples, text, rel, attributes)
+            out.append((pred, gens[i], self._keep(len(z), nodes_added, manipulated)))
+        return out
+
+    @torch.no_grad()
+    def decoder_with_changes_many(self, entries, gen_shape: bool = True, ddim_steps: int = 100,
+                                  launch_B: Optional[int] = None, shape_nodes: str = "all"):
+        """Extension: `decoder_with_changes` for SEVERAL decodes with ONE coalesced sampler + VQ decode.  entries: dicts of
+        the per-scene call's arguments by name (z, dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
+        dec_sdfs, missing_nodes, manipulated_nodes[, attributes, distribution, x_T]).  Returns [(pred, gen_sdf | None,
+        keep)] in entry order, what the per-scene call returns.  shape_nodes='changed' samples only the nodes with keep == 0
+        and a non-zero dec_sdfs row and returns (gen_sdf, node_ids) in gen_sdf's place; 'all' is the reference's behaviour.
+        The RNG contract is _manipulation_many's."""
+        return self._manipulation_many(entries, True, gen_shape, ddim_steps, launch_B, shape_nodes)
+
+    @torch.no_grad()
+    def decoder_with_additions_many(self, entries, gen_shape: bool = True, ddim_steps: int = 100,
+                                    launch_B: Optional[int] = None, shape_nodes: str = "all"):
+        """Extension: `decoder_with_additions` for several decodes, as decoder_with_changes_many (entries name `objs` /
+        `triples` as the per-scene call does; either spelling is read)."""
+        return self._manipulation_many(entries, False, gen_shape, ddim_steps, launch_B, shape_nodes)

@@ -183,6 +183,31 @@ class VAE:
                                                           (self.mean_est_box, self.cov_est_box))
         return boxes, None, keep
 
+    def _manipulation_many(self, per_scene, many, entries, gen_shape, ddim_steps, launch_B, shape_nodes):
+        if self.type_ == "v2_box":                  # the box model has no shapes: its per-scene answers, None shapes
+            names = ("z_box", "z_shape", "objs", "triples", "encoded_dec_text_feat", "encoded_dec_rel_feat", "dec_sdfs",
+                     "attributes", "missing_nodes", "manipulated_nodes")
+            return [per_scene(*[e.get(n) for n in names]) for e in entries]
+        return many(entries, gen_shape=gen_shape, ddim_steps=ddim_steps, launch_B=launch_B, shape_nodes=shape_nodes)
+
+    def decoder_with_changes_boxes_and_shape_many(self, entries, gen_shape=True, ddim_steps: int = 100, launch_B=None,
+                                                  shape_nodes: str = "all"):
+        """Extension: decoder_with_changes_boxes_and_shape for a LIST of decodes -- each a dict of its arguments by name
+        (z_box, objs, triples, encoded_dec_text_feat, encoded_dec_rel_feat, dec_sdfs, attributes, missing_nodes,
+        manipulated_nodes[, distribution, x_T]) -- with every graph through the GCNs on its own and ONE coalesced sampler
+        over all entries' shaped objects (Sg2ScVAEModel.decoder_with_changes_many, whose RNG contract holds here).
+        Returns [(boxes_or_(boxes, angles), gen_sdf | None, keep)] in entry order."""
+        return self._manipulation_many(self.decoder_with_changes_boxes_and_shape,
+                                       None if self.type_ == "v2_box" else self.vae_v2.decoder_with_changes_many,
+                                       entries, gen_shape, ddim_steps, launch_B, shape_nodes)
+
+    def decoder_with_additions_boxes_and_shape_many(self, entries, gen_shape=True, ddim_steps: int = 100, launch_B=None,
+                                                    shape_nodes: str = "all"):
+        """Extension: decoder_with_additions_boxes_and_shape for a list of decodes, as the `changes` twin above."""
+        return self._manipulation_many(self.decoder_with_additions_boxes_and_shape,
+                                       None if self.type_ == "v2_box" else self.vae_v2.decoder_with_additions_many,
+                                       entries, gen_shape, ddim_steps, launch_B, shape_nodes)
+
     def decoder_boxes(self, z, objs, triples, attributes, encoded_dec_text_feat=None, encoded_dec_rel_feat=None):
         """model/VAE.py:226-233 (whose v2 call lacks the CLIP features the v2 decoder needs; required here)."""
         if self.type_ != "v2_box":

@@ -829,7 +829,7 @@ def _constraint_verdicts(M, vocab, b, t, **kw):
     return np.array(acc["total"], np.int8)
 
 
-def _stable_scenes(M, vocab, rng, scenes, with_norm):
+def _stable_scenes(M, vocab, rng, scenes, with_norm, **kw):
     """drop the triples whose reference verdict (strict or not) moves under +-1e-5 noise on every box entry (two draws), or --
     for unnormalised boxes, where the reference compares in fp32 -- when the fp32 box is widened to fp64 first"""
     out, dropped = [], 0
@@ -837,12 +837,12 @@ def _stable_scenes(M, vocab, rng, scenes, with_norm):
         ev = t[:, 1] != 0
         bad = np.zeros(int(ev.sum()), bool)
         for strict in (True, False):
-            base = _constraint_verdicts(M, vocab, b, t, with_norm=with_norm, strict=strict)
+            base = _constraint_verdicts(M, vocab, b, t, with_norm=with_norm, strict=strict, **kw)
             trials = [(b.astype(np.float64) + rng.uniform(-1e-5, 1e-5, b.shape)).astype(np.float32) for _ in range(2)]
             if not with_norm:
                 trials.append(b.astype(np.float64))
             for nb in trials:
-                bad |= _constraint_verdicts(M, vocab, nb, t, with_norm=with_norm, strict=strict) != base
+                bad |= _constraint_verdicts(M, vocab, nb, t, with_norm=with_norm, strict=strict, **kw) != base
         drop = np.zeros(len(t), bool)
         drop[np.flatnonzero(ev)[bad]] = True
         dropped += int(drop.sum())
@@ -1247,6 +1247,153 @@ def g_diversity():
     save("diversity", **out)
 
 
+MANIP_CLASSES = ["_scene_", "bed", "cabinet", "chair", "floor", "lamp", "nightstand", "sofa", "table", "wardrobe"]
+MANIP_SEEDS = 6
+
+
+def _manip_graphs(rng):
+    """eight small graphs (objs, triples): six ordinary ones, one of `floor` nodes only, one whose triples are `in` edges or
+    touch the floor (nothing to edit)"""
+    floor = MANIP_CLASSES.index("floor")
+    out = []
+    for _ in range(6):
+        n = int(rng.integers(3, 8))
+        cls = [c for c in range(1, len(MANIP_CLASSES)) if c != floor]
+        objs = [int(rng.choice(cls)) for _ in range(n)] + [floor, 0]
+        tri = []
+        for s in range(n + 1):
+            for _ in range(int(rng.integers(1, 4))):
+                o = int(rng.integers(0, n + 1))
+                if o != s:
+                    tri.append([s, int(rng.integers(1, 16)), o])
+        tri.append(list(tri[int(rng.integers(0, len(tri)))]))          # a repeated triple
+        tri += [[i, 0, n + 1] for i in range(n + 1)]
+        out.append((objs, tri))
+    out.append(([floor, floor, floor, 0], [[0, 1, 1], [1, 5, 2], [0, 0, 3], [1, 0, 3], [2, 0, 3]]))
+    out.append(([1, 3, floor, 0], [[0, 2, 2], [2, 9, 1], [0, 0, 3], [1, 0, 3], [2, 0, 3]]))
+    return out
+
+
+def g_manipulation():
+    """tests/golden/manipulation.npz: (a) what the dataset's remove_node_and_relationship / modify_relship
+    (dataset/threedfront_dataset.py:582-684) do to eight graphs under six seeds, called unbound on a namespace; (b) twelve
+    constraint scenes with a ground-truth box set and keep masks, and the three lists scripts/eval_3dfront.py:411-416
+    accumulates for them.  The conditions the tests lean on are asserted here: statements about the reference alone."""
+    import copy
+    for name in ("tqdm",):
+        try:
+            __import__(name)
+        except ImportError:
+            sys.modules[name] = mock.MagicMock(name=name)
+    import dataset.threedfront_dataset as TD
+    import helpers.metrics_3dfront as M
+    from commonscenes_amd.manipulation import SGFRONT_RELATIONSHIPS, graph_lists
+    rels = list(SGFRONT_RELATIONSHIPS)
+    classes = {n: i for i, n in enumerate(MANIP_CLASSES)}
+    classes_r = {i: n for n, i in classes.items()}
+    ns = types.SimpleNamespace(classes=classes, relationships_dict=dict(zip(rels, range(1, len(rels) + 1))),
+                               with_feats=False, with_CLIP=True)
+    ns.relationships_dict_r = {v: k for k, v in ns.relationships_dict.items()}
+    graphs = _manip_graphs(np.random.default_rng(5))
+    G, S = len(graphs), MANIP_SEEDS
+    maxO, maxT = max(len(o) for o, _ in graphs), max(len(t) for _, t in graphs)
+    arrs = dict(in_objs=np.full((G, maxO), -1, np.int64), in_triples=np.full((G, maxT, 3), -1, np.int64),
+                in_n=np.array([[len(o), len(t)] for o, t in graphs], np.int64),
+                rm_node=np.zeros((G, S), np.int64), rm_objs=np.full((G, S, maxO), -1, np.int64),
+                rm_obj_rows=np.full((G, S, maxO), -1, np.int64), rm_triples=np.full((G, S, maxT, 3), -1, np.int64),
+                rm_tri_rows=np.full((G, S, maxT), -1, np.int64), rm_word_rows=np.full((G, S, maxT), -1, np.int64))
+    for tag in ("mod0", "mod1"):
+        arrs.update({f"{tag}_idx": np.zeros((G, S), np.int64), f"{tag}_pair": np.zeros((G, S, 2), np.int64),
+                     f"{tag}_new_pred": np.zeros((G, S), np.int64), f"{tag}_did": np.zeros((G, S), bool),
+                     f"{tag}_triples": np.full((G, S, maxT, 3), -1, np.int64)})
+    words = {"mod0": [], "mod1": []}
+    for gi, (objs, tri) in enumerate(graphs):
+        arrs["in_objs"][gi, :len(objs)] = objs
+        arrs["in_triples"][gi, :len(tri)] = tri
+        O, T = len(objs), len(tri)
+        base = graph_lists(objs, tri, [[float(i)] * 7 for i in range(O)], np.arange(O, dtype=np.float32).reshape(O, 1),
+                           np.arange(T, dtype=np.float32).reshape(T, 1), classes_r, rels)
+        tagged = [f"{i}|{w}" for i, w in enumerate(base["words"])]
+        for k in range(S):
+            g = copy.deepcopy(base)
+            g["words"] = list(tagged)
+            np.random.seed(k)
+            node = TD.ThreedFrontDatasetSceneGraph.remove_node_and_relationship(ns, g)
+            arrs["rm_node"][gi, k] = node
+            arrs["rm_objs"][gi, k, :len(g["objs"])] = g["objs"]
+            arrs["rm_obj_rows"][gi, k, :len(g["boxes"])] = [int(b[0]) for b in g["boxes"]]
+            assert [int(f[0]) for f in g["text_feats"]] == [int(b[0]) for b in g["boxes"]]
+            arrs["rm_triples"][gi, k, :len(g["triples"])] = np.array(g["triples"], np.int64).reshape(-1, 3)
+            arrs["rm_tri_rows"][gi, k, :len(g["rel_feats"])] = [int(f[0]) for f in g["rel_feats"]]
+            arrs["rm_word_rows"][gi, k, :len(g["words"])] = [int(w.split("|")[0]) for w in g["words"]]
+            for tag, interp in (("mod0", False), ("mod1", True)):
+                g = copy.deepcopy(base)
+                np.random.seed(k)
+                idx, pair, did = TD.ThreedFrontDatasetSceneGraph.modify_relship(ns, g, interpretable=interp)
+                arrs[f"{tag}_idx"][gi, k], arrs[f"{tag}_pair"][gi, k], arrs[f"{tag}_did"][gi, k] = idx, pair, did
+                arrs[f"{tag}_new_pred"][gi, k] = g["triples"][idx][1]
+                arrs[f"{tag}_triples"][gi, k, :T] = g["triples"]
+                assert (g.get("changed_id") == idx) == bool(did) or not did
+                words[tag].append("\n".join(g["words"]))
+    assert (arrs["rm_node"][6] == -1).all() and not arrs["mod0_did"][7].any() and not arrs["mod1_did"][7].any()
+    assert (arrs["rm_node"][:6] >= 0).all() and arrs["mod0_did"][:6].all()
+    print(f"[manipulation] edits: removed nodes {arrs['rm_node'].tolist()}, interpretable edits that changed "
+          f"{int(arrs['mod1_did'].sum())} / {G * S}", flush=True)
+
+    # ---- the three tables ----
+    vocab = {"pred_idx_to_name": [p + "\n" for p in CONSTRAINT_PREDS]}
+    stats = np.stack([BOX_MEAN * 1.05 + 0.02, BOX_STD * 0.93])
+    with tempfile.TemporaryDirectory() as td:
+        f = os.path.join(td, "boxes_stats.txt")
+        np.savetxt(f, stats)
+        for seed in range(31, 71):
+            rng = np.random.default_rng(seed)
+            try:
+                raw = [_constraint_scene(rng, 6, True) for _ in range(12)]
+                gts = [(b.astype(np.float64) + rng.normal(0, 0.25, b.shape)).astype(np.float32) for b, _, _ in raw]
+                total = sum(len(t) for _, t, _ in raw)
+                sc, d0 = _stable_scenes(M, vocab, rng, raw, True)
+                sc, d1 = _stable_scenes(M, vocab, rng, sc, True, file_dist=f)
+                bps = [np.where(k[:, None] == 0, b, g) for (b, _, k), g in zip(sc, gts)]
+                sb, d2 = _stable_scenes(M, vocab, rng, [(bp, t, k) for bp, (_, t, k) in zip(bps, sc)], True, file_dist=f)
+                sc = [(b, t, k) for (b, _, k), (_, t, _) in zip(sc, sb)]
+                accs = [{k: [] for k in CONSTRAINT_KEYS} for _ in range(3)]
+                lens = np.zeros((3, 12, 12), np.int64)
+                for si, ((b, t, k), g, bp) in enumerate(zip(sc, gts, bps)):
+                    tt, kk = torch.from_numpy(t), torch.from_numpy(k).float().reshape(-1, 1)
+                    before = [[len(a[key]) for key in CONSTRAINT_KEYS] for a in accs]
+                    M.validate_constrains_changes(tt, torch.from_numpy(b), torch.from_numpy(g), kk, vocab, accs[0],
+                                                  file_dist=f, with_norm=True)                      # eval_3dfront.py:411-416
+                    M.validate_constrains_changes(tt, torch.from_numpy(bp), torch.from_numpy(g), kk, vocab, accs[2],
+                                                  file_dist=f, with_norm=True)
+                    M.validate_constrains(tt, torch.from_numpy(b), torch.from_numpy(g), kk, vocab, accs[1], with_norm=True)
+                    for ti in range(3):
+                        lens[ti, si] = [len(accs[ti][key]) - before[ti][j] for j, key in enumerate(CONSTRAINT_KEYS)]
+            except Exception as e:
+                print(f"[manipulation] seed {seed}: the reference raised {type(e).__name__}: {e}", flush=True)
+                continue
+            dropped = d0 + d1 + d2
+            per = [[(int(np.sum(np.asarray(a[k]) == 0)), int(np.sum(np.asarray(a[k]) == 1))) for k in CONSTRAINT_KEYS[:11]]
+                   for a in accs]
+            worst = min(min(min(c) for c in p) for p in per)
+            print(f"[manipulation] seed {seed}: {total - dropped} triples ({dropped} dropped), fewest verdicts of one kind in "
+                  f"a category {worst}", flush=True)
+            if dropped / total <= 0.02 and worst >= 5:
+                break
+        else:
+            raise SystemExit("no seed satisfies the fixture's conditions")
+    boxes, tri, keep, bp_, tp_ = _pack_scenes(sc)
+    for ti, tag in enumerate(("changed", "unchanged", "orig")):
+        arrs[f"acc_{tag}"], arrs[f"len_{tag}"] = _pack_lists(accs[ti])
+        arrs[f"scene_len_{tag}"] = lens[ti]
+    save("manipulation", classes=np.array(MANIP_CLASSES), relationships=np.array(rels), seeds=np.int64(S),
+         mod0_words=np.array(words["mod0"]).reshape(G, S), mod1_words=np.array(words["mod1"]).reshape(G, S),
+         t_boxes=boxes, t_gt=np.concatenate(gts), t_triples=tri, t_keep=keep, t_box_ptr=bp_, t_triple_ptr=tp_, t_stats=stats,
+         t_seed=np.int64(seed), t_dropped_fraction=np.float64(dropped / total), t_min_per_verdict=np.int64(worst),
+         pred_names=np.array(CONSTRAINT_PREDS), keys=np.array(CONSTRAINT_KEYS), **arrs)
+    assert (OUT / "manipulation.npz").stat().st_size < 200_000
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -1256,7 +1403,7 @@ def main():
     todo = a.only or ["schedule", "unet_small", "unet_full", "ddim_small", "ddim_full", "vq", "gcn", "e2e",
                       "unet_concat_small", "unet_concat_full", "ddim_concat_small", "gcn_concat", "e2e_concat", "box",
                       "full_manip", "e2e_full", "traj_small", "traj_full", "plms", "traj100_full", "e2e100_small", "e2e100_full", "vq_encode", "shape_metrics",
-                      "constraints", "eval_losses", "shape_comp", "diversity"]
+                      "constraints", "eval_losses", "shape_comp", "diversity", "manipulation"]
     with tempfile.TemporaryDirectory() as td:
         tmp = Path(td)
         for name in todo:
@@ -1317,6 +1464,8 @@ def main():
                 g_shape_comp(tmp)
             elif name == "diversity":
                 g_diversity()
+            elif name == "manipulation":
+                g_manipulation()
             else:
                 raise SystemExit(f"unknown fixture {name}")
 
