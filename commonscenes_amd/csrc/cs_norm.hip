@@ -14,6 +14,40 @@ constexpr int64_t GN_SMALL_BYTES = 16 << 20;   // single-launch path: whole tens
 constexpr int64_t GN_SMALL_GROUP = 11264;      // ... and at most this many elements per (sample, group) workgroup
                                                // (16x4x4 voxels x 42 channels: 14.5 vs 18.0 / 25.4 vs 30.2 us, tools/gn_bench.py)
 
+// The thread map of the row and line kernels: a thread keeps a column of V channels; a workgroup of 256 puts `tpr` threads on
+// a row (line) of cv = c / V columns and walks `lanes` rows (lines) side by side.  Threads past tpr * lanes idle.
+struct GnMap {
+  int tpr, lanes;
+};
+__host__ __device__ __forceinline__ GnMap gn_map(int cv) {
+  const int tpr = cv < 256 ? cv : 256;
+  return {tpr, 256 / tpr};
+}
+
+// (mean, variance clamped at 0, 1 / std) of a group from its fp64 (sum, sum of squares)
+__device__ __forceinline__ void gn_moments(double s, double q, double count, float eps, double& mean, double& var,
+                                           float& rstd) {
+  mean = s / count;
+  var = q / count - mean * mean;
+  if (var < 0) var = 0;
+  rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// |mean| + std * sqrt(n - 1) >= max |x| over the group (Samuelson's inequality), rounded UP to fp32; the maximum over all
+// (sample, group)s bounds the tensor: what CsConvGemm.a_bound reads.  atomicMax of the bits: order-independent.
+__device__ __forceinline__ float gn_bound_value(double mean, double var, double count) {
+  const double b = fabs(mean) + sqrt(var * (count > 1.0 ? count - 1.0 : 1.0));
+  float bf = (float)b;
+  if ((double)bf < b) bf = __uint_as_float(__float_as_uint(bf) + 1u);
+  return (bf == bf && bf > 0.f) ? bf : 0.f;
+}
+__device__ __forceinline__ void gn_bound_commit(float* bound, float bf) {
+  if (bf > 0.f) atomicMax(reinterpret_cast<unsigned int*>(bound), __float_as_uint(bf));
+}
+__device__ __forceinline__ void gn_bound_max(float* bound, double mean, double var, double count) {
+  gn_bound_commit(bound, gn_bound_value(mean, var, count));
+}
+
 // Pass 1: partial[n][split][g] = (sum, sumsq) in fp64.  Each thread owns fixed channel chunks so
 // its accumulation order is fixed; the cross-thread reduction runs in a fixed order too, so the
 // statistics are bit-reproducible run to run.
@@ -24,8 +58,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
   const int n = blockIdx.x / nsplit;
   const int split = blockIdx.x % nsplit;
   const int ch4 = c >> 2;
-  const int tpr = ch4 < 256 ? ch4 : 256;  // threads per row
-  const int rowlanes = 256 / tpr;
+  const int tpr = gn_map(ch4).tpr, rowlanes = gn_map(ch4).lanes;
   const int tid = threadIdx.x;
   const int rl = tid / tpr;
   const int cl = tid - rl * tpr;
@@ -78,8 +111,6 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
 // One wave per (sample, group): lanes take the row-slice partials in a strided fashion and a fixed butterfly
 // combines them, so the result does not depend on scheduling (the serial version walked up to 256 dependent
 // loads per thread: 17-27 us for what is a few KB of data).
-__device__ __forceinline__ void gn_bound_max(float* bound, double mean, double var, double count);
-
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ partial, int nsplit, int groups,
                                                           double count, float eps, float* __restrict__ stats,
                                                           int total, float* __restrict__ bound = nullptr) {
@@ -99,11 +130,11 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restri
     q += __shfl_xor(q, o, 64);
   }
   if (lane == 0) {
-    const double mean = s / count;
-    double var = q / count - mean * mean;
-    if (var < 0) var = 0;
+    double mean, var;
+    float rstd;
+    gn_moments(s, q, count, eps, mean, var, rstd);
     stats[2 * i] = (float)mean;
-    stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    stats[2 * i + 1] = rstd;
     if (bound) gn_bound_max(bound, mean, var, count);
   }
 }
@@ -157,21 +188,6 @@ __device__ __forceinline__ void gn_group_parts(const GnSegs& sg, int n, int g, i
   }
 }
 
-// |mean| + std * sqrt(n - 1) >= max |x| over the group (Samuelson's inequality), rounded UP to fp32; the maximum over all
-// (sample, group)s bounds the tensor: what CsConvGemm.a_bound reads.  atomicMax of the bits: order-independent.
-__device__ __forceinline__ float gn_bound_value(double mean, double var, double count) {
-  const double b = fabs(mean) + sqrt(var * (count > 1.0 ? count - 1.0 : 1.0));
-  float bf = (float)b;
-  if ((double)bf < b) bf = __uint_as_float(__float_as_uint(bf) + 1u);
-  return (bf == bf && bf > 0.f) ? bf : 0.f;
-}
-__device__ __forceinline__ void gn_bound_commit(float* bound, float bf) {
-  if (bf > 0.f) atomicMax(reinterpret_cast<unsigned int*>(bound), __float_as_uint(bf));
-}
-__device__ __forceinline__ void gn_bound_max(float* bound, double mean, double var, double count) {
-  gn_bound_commit(bound, gn_bound_value(mean, var, count));
-}
-
 // One word per tensor: the 2048 (sample, group)s of a 32-object launch each hitting it with an atomic serialise in L2
 // (measured: 30 us for a kernel that otherwise takes 5), so a workgroup is SIXTEEN waves = sixteen (sample, group)s and
 // commits one maximum.
@@ -218,12 +234,12 @@ __global__ __launch_bounds__(64 * GN_FIN_WAVES) void gn_finalize_parts_kernel(co
     }
   }
   if (i < total && sub == 0) {
-    const double mean = s / count;
-    double var = q / count - mean * mean;
-    if (var < 0) var = 0;
+    double mean, var;
+    float rstd;
+    gn_moments(s, q, count, eps, mean, var, rstd);
     if (lane == 0 && stats) {
       stats[2 * i] = (float)mean;
-      stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+      stats[2 * i + 1] = rstd;
     }
     if (bound) bf = gn_bound_value(mean, var, count);
   }
@@ -238,21 +254,58 @@ __global__ __launch_bounds__(64 * GN_FIN_WAVES) void gn_finalize_parts_kernel(co
   }
 }
 
+// What a thread of the apply kernels keeps for its V channels, loaded once: the affine parameters and the statistics of each
+// channel's group.  The c channels handled are channels ch0 .. ch0 + c of the normalised tensor -- x, gamma and beta already
+// point at channel ch0 -- so the thread's channel col + k belongs to group (ch0 + col + k) / cpg; `st` = the sample's
+// [groups][2] (mean, rstd).
+template <int V>
+struct GnCols {
+  float g[V], b[V], mean[V], rstd[V];
+  __device__ __forceinline__ GnCols(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                    const float* __restrict__ st, int ch0, int cpg, int col) {
+#pragma unroll
+    for (int k4 = 0; k4 < V / 4; ++k4) {
+      const float4 gv = *reinterpret_cast<const float4*>(gamma + col + 4 * k4);
+      const float4 bv = *reinterpret_cast<const float4*>(beta + col + 4 * k4);
+      g[4 * k4] = gv.x; g[4 * k4 + 1] = gv.y; g[4 * k4 + 2] = gv.z; g[4 * k4 + 3] = gv.w;
+      b[4 * k4] = bv.x; b[4 * k4 + 1] = bv.y; b[4 * k4 + 2] = bv.z; b[4 * k4 + 3] = bv.w;
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const int grp = (ch0 + col + k) / cpg;
+      mean[k] = st[grp * 2];
+      rstd[k] = st[grp * 2 + 1];
+    }
+  }
+  // THE expression of every GroupNorm apply: channel k of the thread's column
+  __device__ __forceinline__ float norm(float in, int k, int act) const {
+    return cs_act((in - mean[k]) * rstd[k] * g[k] + b[k], act);
+  }
+  // the V channels at px, normalised and scaled (the operand scale is applied after the activation)
+  __device__ __forceinline__ void norm_scaled(const float* __restrict__ px, int act, float a_scale, float (&o)[V]) const {
+#pragma unroll
+    for (int k4 = 0; k4 < V / 4; ++k4) {
+      const float4 v = *reinterpret_cast<const float4*>(px + 4 * k4);
+      const float iv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[4 * k4 + k] = norm(iv[k], 4 * k4 + k, act) * a_scale;
+    }
+  }
+};
+
 // One workgroup = a run of rows of ONE sample; a thread keeps its float4 column for the whole run, so the group
 // statistics and the affine parameters of its four channels are loaded once and the row loop has no index
-// arithmetic beyond a pointer bump (the previous flat element loop spent its time in 64-bit divisions: 45 % of the
-// HBM rate).  Four rows' loads are in flight per thread.
-__global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x,
-                                                       const float* __restrict__ stats,
-                                                       const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta,
-                                                       float* __restrict__ y, int rows, int c, int ldx, int ldy,
-                                                       int groups, int act, int rows_per_block, int cpg, int ch0) {
-  // (`groups` = row length of `stats`; the c channels handled here are channels ch0 .. ch0 + c of the normalised
-  // tensor -- x, gamma, beta and y already point at channel ch0 -- so channel k belongs to group (ch0 + k) / cpg)
+// arithmetic beyond a pointer bump (the previous flat element loop -- in both output forms, two 64-bit divisions per
+// float4 -- ran at ~45 % of the HBM rate).  Four rows' loads are in flight per thread.
+// (`groups` = row length of `stats`.)  put(off, o) stores the four normalised channels o of the sample's output element
+// at off = row ldy + column: the ONE difference between the two kernels below.
+template <class Put>
+__device__ __forceinline__ void gn_apply_rows(const float* __restrict__ x, const float* __restrict__ stats,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta, int rows,
+                                              int c, int ldx, int ldy, int groups, int act, int rows_per_block, int cpg,
+                                              int ch0, Put put) {
   const int ch4 = c >> 2;
-  const int tpr = ch4 < 256 ? ch4 : 256;   // threads per row
-  const int rowlanes = 256 / tpr;
+  const int tpr = gn_map(ch4).tpr, rowlanes = gn_map(ch4).lanes;
   const int tid = threadIdx.x;
   const int rl = tid / tpr;
   const int cl = tid - rl * tpr;
@@ -261,20 +314,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   const int r0 = blockIdx.x * rows_per_block;
   const int r1 = min(rows, r0 + rows_per_block);
   const float* xb = x + (int64_t)n * rows * ldx;
-  float* yb = y + (int64_t)n * rows * ldy;
   const float* st = stats + (int64_t)n * groups * 2;
   for (int c4 = cl; c4 < ch4; c4 += tpr) {
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c4 * 4);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c4 * 4);
-    const float gg[4] = {g.x, g.y, g.z, g.w};
-    const float bb[4] = {b.x, b.y, b.z, b.w};
-    float mean[4], rstd[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int grp = (ch0 + c4 * 4 + k) / cpg;
-      mean[k] = st[grp * 2];
-      rstd[k] = st[grp * 2 + 1];
-    }
+    const GnCols<4> cols(gamma, beta, st, ch0, cpg, c4 * 4);
     for (int r = r0 + rl; r < r1; r += 4 * rowlanes) {
       float4 v[4];
 #pragma unroll
@@ -289,21 +331,31 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
           const float in[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
           float o[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) o[k] = cs_act((in[k] - mean[k]) * rstd[k] * gg[k] + bb[k], act);
-          *reinterpret_cast<float4*>(yb + (int64_t)rr * ldy + c4 * 4) = make_float4(o[0], o[1], o[2], o[3]);
+          for (int k = 0; k < 4; ++k) o[k] = cols.norm(in[k], k, act);
+          put((int64_t)rr * ldy + c4 * 4, o);
         }
       }
     }
   }
 }
 
+// fp32 output
+__global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x,
+                                                       const float* __restrict__ stats,
+                                                       const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta,
+                                                       float* __restrict__ y, int rows, int c, int ldx, int ldy,
+                                                       int groups, int act, int rows_per_block, int cpg, int ch0) {
+  float* yb = y + (int64_t)blockIdx.y * rows * ldy;
+  gn_apply_rows(x, stats, gamma, beta, rows, c, ldx, ldy, groups, act, rows_per_block, cpg, ch0,
+                [&](int64_t off, const float (&o)[4]) {
+                  *reinterpret_cast<float4*>(yb + off) = make_float4(o[0], o[1], o[2], o[3]);
+                });
+}
+
 // GroupNorm apply emitting the fp16 hi / lo pair of y * a_scale (A operand of the F16X3 GEMMs): the fp32 -> pair
 // split costs nothing here (this kernel is HBM-bound) and is then done once per element instead of once per
 // conv tap inside the GEMM.  Output bytes equal the fp32 version (2 + 2 per element).
-typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-// Same decomposition as gn_apply_kernel (a workgroup = a run of rows of one sample, a thread keeps its float4 column:
-// statistics and affine parameters loaded once, four rows' loads in flight); the first version walked a flat element
-// index with two 64-bit divisions per float4 and ran at ~45 % of the HBM rate.
 __global__ __launch_bounds__(256) void gn_apply_split16_kernel(const float* __restrict__ x,
                                                                const float* __restrict__ stats,
                                                                const float* __restrict__ gamma,
@@ -312,164 +364,55 @@ __global__ __launch_bounds__(256) void gn_apply_split16_kernel(const float* __re
                                                                int rows, int c, int ldx, int ldy, int groups,
                                                                int act, float a_scale, int rows_per_block,
                                                                int32_t* __restrict__ status, int cpg, int ch0) {
-  const int ch4 = c >> 2;
-  const int tpr = ch4 < 256 ? ch4 : 256;   // threads per row
-  const int rowlanes = 256 / tpr;
-  const int tid = threadIdx.x;
-  const int rl = tid / tpr;
-  const int cl = tid - rl * tpr;
-  if (rl >= rowlanes) return;
-  const int n = blockIdx.y;
-  const int r0 = blockIdx.x * rows_per_block;
-  const int r1 = min(rows, r0 + rows_per_block);
-  const float* xb = x + (int64_t)n * rows * ldx;
-  _Float16* hb = yh + (int64_t)n * rows * ldy;
-  _Float16* lb = yl + (int64_t)n * rows * ldy;
-  const float* st = stats + (int64_t)n * groups * 2;
+  _Float16* hb = yh + (int64_t)blockIdx.y * rows * ldy;
+  _Float16* lb = yl + (int64_t)blockIdx.y * rows * ldy;
   float amax = 0.f;
-  for (int c4 = cl; c4 < ch4; c4 += tpr) {
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c4 * 4);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c4 * 4);
-    const float gg[4] = {g.x, g.y, g.z, g.w};
-    const float bb[4] = {b.x, b.y, b.z, b.w};
-    float mean[4], rstd[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int grp = (ch0 + c4 * 4 + k) / cpg;
-      mean[k] = st[grp * 2];
-      rstd[k] = st[grp * 2 + 1];
-    }
-    for (int r = r0 + rl; r < r1; r += 4 * rowlanes) {
-      float4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int rr = r + u * rowlanes;
-        if (rr < r1) v[u] = *reinterpret_cast<const float4*>(xb + (int64_t)rr * ldx + c4 * 4);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int rr = r + u * rowlanes;
-        if (rr < r1) {
-          const float in[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-          h4v hi, lo;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float o = cs_act((in[k] - mean[k]) * rstd[k] * gg[k] + bb[k], act) * a_scale;
-            amax = fmaxf(amax, fabsf(o));
-            const _Float16 h = (_Float16)o;
-            hi[k] = h;
-            lo[k] = (_Float16)(o - (float)h);
-          }
-          *reinterpret_cast<h4v*>(hb + (int64_t)rr * ldy + c4 * 4) = hi;
-          *reinterpret_cast<h4v*>(lb + (int64_t)rr * ldy + c4 * 4) = lo;
-        }
-      }
-    }
-  }
-  if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
+  gn_apply_rows(x, stats, gamma, beta, rows, c, ldx, ldy, groups, act, rows_per_block, cpg, ch0,
+                [&](int64_t off, const float (&o)[4]) {
+                  const float os[4] = {o[0] * a_scale, o[1] * a_scale, o[2] * a_scale, o[3] * a_scale};
+                  cs_hv<4> hi, lo;
+                  cs_pair_split<4>(os, hi, lo, amax);
+                  *reinterpret_cast<cs_hv<4>*>(hb + off) = hi;
+                  *reinterpret_cast<cs_hv<4>*>(lb + off) = lo;
+                });
+  cs_pair_amax_flag(status, amax);
 }
 
-// r5: GroupNorm + activation emitted in the WINOGRAD-W form of the 3x3x3 conv that follows (CsConvGemm.a_format = 3): per W
-// line of a sample and pair of voxels (w = 2 w2, 2 w2 + 1) the four transformed values [d0 - d2, d1 + d2, d2 - d1, d1 - d3] of
-// d_j = y[w - 1 + j] (0 outside the line), split into fp16 hi / lo of value * a_scale -- images [4][nb][lines][W/2][ldv].
-// A thread keeps its float4 column and walks whole lines: every activation is evaluated once (a pair's d2, d3 are the
-// next pair's d0, d1).
-__global__ __launch_bounds__(256) void gn_apply_wino16_kernel(const float* __restrict__ x, const float* __restrict__ stats,
-                                                              const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, _Float16* __restrict__ vh,
-                                                              _Float16* __restrict__ vl, int lines, int w, int c, int ldx,
-                                                              int ldv, int groups, int act, float a_scale,
-                                                              int lines_per_block, int64_t pos_stride,
-                                                              int32_t* __restrict__ status, int cpg, int ch0) {
-  const int ch4 = c >> 2;
-  const int tpr = ch4 < 256 ? ch4 : 256;   // threads per line
-  const int linelanes = 256 / tpr;
-  const int tid = threadIdx.x;
-  const int ll = tid / tpr;
-  const int cl = tid - ll * tpr;
-  if (ll >= linelanes) return;
-  const int n = blockIdx.y;
-  const int l0 = blockIdx.x * lines_per_block;
-  const int l1 = min(lines, l0 + lines_per_block);
-  const int w2n = w >> 1;
-  const float* xb = x + (int64_t)n * lines * w * ldx;
-  const int64_t vrow0 = (int64_t)n * lines * w2n;
-  const float* st = stats + (int64_t)n * groups * 2;
-  float amax = 0.f;
-  for (int c4 = cl; c4 < ch4; c4 += tpr) {
-    const float4 g = *reinterpret_cast<const float4*>(gamma + c4 * 4);
-    const float4 b = *reinterpret_cast<const float4*>(beta + c4 * 4);
-    const float gg[4] = {g.x, g.y, g.z, g.w};
-    const float bb[4] = {b.x, b.y, b.z, b.w};
-    float mean[4], rstd[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int grp = (ch0 + c4 * 4 + k) / cpg;
-      mean[k] = st[grp * 2];
-      rstd[k] = st[grp * 2 + 1];
-    }
-    auto actv = [&](const float4 v, float (&o)[4]) {
-      const float in[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = cs_act((in[k] - mean[k]) * rstd[k] * gg[k] + bb[k], act) * a_scale;
-    };
-    for (int line = l0 + ll; line < l1; line += linelanes) {
-      const float* xl = xb + (int64_t)line * w * ldx + c4 * 4;
-      float d0[4] = {0.f, 0.f, 0.f, 0.f}, d1[4], d2[4], d3[4];
-      actv(*reinterpret_cast<const float4*>(xl), d1);
-      for (int w2 = 0; w2 < w2n; ++w2) {
-        actv(*reinterpret_cast<const float4*>(xl + (int64_t)(2 * w2 + 1) * ldx), d2);
-        if (2 * w2 + 2 < w) {
-          actv(*reinterpret_cast<const float4*>(xl + (int64_t)(2 * w2 + 2) * ldx), d3);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) d3[k] = 0.f;
-        }
-        const int64_t off = (vrow0 + (int64_t)line * w2n + w2) * ldv + c4 * 4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          h4v hi, lo;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float o = q == 0 ? d0[k] - d2[k] : q == 1 ? d1[k] + d2[k] : q == 2 ? d2[k] - d1[k] : d1[k] - d3[k];
-            amax = fmaxf(amax, fabsf(o));
-            const _Float16 hh = (_Float16)o;
-            hi[k] = hh;
-            lo[k] = (_Float16)(o - (float)hh);
-          }
-          *reinterpret_cast<h4v*>(vh + q * pos_stride + off) = hi;
-          *reinterpret_cast<h4v*>(vl + q * pos_stride + off) = lo;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          d0[k] = d2[k];
-          d1[k] = d3[k];
-        }
-      }
-    }
+// Image q of the Winograd transform B^T d along W, channel k of the thread's column; d_j = y[VAR t - 1 + j] of tile t (0
+// outside the line).  F(2,3): [d0 - d2, d1 + d2, d2 - d1, d1 - d3].
+template <int VAR, int V>
+__device__ __forceinline__ float gn_wino_bt(const float (&d)[VAR + 2][V], int q, int k) {
+  if constexpr (VAR == 2) {
+    return q == 0 ? d[0][k] - d[2][k] : q == 1 ? d[1][k] + d[2][k] : q == 2 ? d[2][k] - d[1][k] : d[1][k] - d[3][k];
+  } else {
+    if (q == 0) return 4.f * d[0][k] - 5.f * d[2][k] + d[4][k];
+    if (q == 1) return (d[4][k] + d[3][k]) - 4.f * (d[1][k] + d[2][k]);
+    if (q == 2) return 4.f * (d[1][k] - d[2][k]) + (d[4][k] - d[3][k]);
+    if (q == 3) return 2.f * (d[3][k] - d[1][k]) + (d[4][k] - d[2][k]);
+    if (q == 4) return 2.f * (d[1][k] - d[3][k]) + (d[4][k] - d[2][k]);
+    return 4.f * d[1][k] - 5.f * d[3][k] + d[5][k];
   }
-  if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
 }
 
-// F(4,3) along W (CsConvGemm.a_format = 4): per W line and FOUR voxels (w = 4 t .. 4 t + 3) the six transformed values B^T d of
-// d_j = y[4 t - 1 + j] (0 outside the line) -- images [6][nb][lines][W/4][ldv].  Same line walk: a tile's d4, d5 are the next
-// tile's d0, d1.
-// (V = channels per thread.  r6 measured V = 8 -- two float4 loads, ONE 16-byte store per image and position instead of two
-// 8-byte ones -- and it LOST: 80.7 vs 61.3 us per launch, 64.63 vs 64.00 ms per 32-object step same box
+// r5: GroupNorm + activation emitted in the WINOGRAD-W form of the 3x3x3 conv that follows: per W line of a sample and tile of
+// VAR voxels (w = VAR t .. VAR t + VAR - 1) the VAR + 2 transformed values B^T d (gn_wino_bt), split into fp16 hi / lo of
+// value * a_scale -- images [VAR + 2][nb][lines][W / VAR][ldv].  VAR = 2: F(2,3), CsConvGemm.a_format = 3; VAR = 4: F(4,3),
+// a_format = 4.  A thread keeps its column of V channels and walks whole lines: every activation is evaluated once (a tile's
+// last two d are the next tile's d0, d1).  w % VAR == 0 (the entry checks it), so only the LAST d of a tile can lie past the
+// line.
+// (V = channels per thread.  r6 measured V = 8 for F(4,3) -- two float4 loads, ONE 16-byte store per image and position
+// instead of two 8-byte ones -- and it LOST: 80.7 vs 61.3 us per launch, 64.63 vs 64.00 ms per 32-object step same box
 // (profiles/r06_j_gn_wino_v8_whatif_ab.txt): half the threads in flight cost more than the wider stores gain.  V = 4 stays;
 // -DCS_GN_WINO_V8 is the what-if build.  Same arithmetic per element either way.)
-template <int V>
-__global__ __launch_bounds__(256) void gn_apply_wino43_kernel(const float* __restrict__ x, const float* __restrict__ stats,
-                                                              const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, _Float16* __restrict__ vh,
-                                                              _Float16* __restrict__ vl, int lines, int w, int c, int ldx,
-                                                              int ldv, int groups, int act, float a_scale,
-                                                              int lines_per_block, int64_t pos_stride,
-                                                              int32_t* __restrict__ status, int cpg, int ch0) {
-  typedef _Float16 hv __attribute__((ext_vector_type(V)));
+template <int VAR, int V>
+__global__ __launch_bounds__(256) void gn_apply_wino_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            _Float16* __restrict__ vh, _Float16* __restrict__ vl, int lines,
+                                                            int w, int c, int ldx, int ldv, int groups, int act,
+                                                            float a_scale, int lines_per_block, int64_t pos_stride,
+                                                            int32_t* __restrict__ status, int cpg, int ch0) {
   const int chv = c / V;
-  const int tpr = chv < 256 ? chv : 256;
-  const int linelanes = 256 / tpr;
+  const int tpr = gn_map(chv).tpr, linelanes = gn_map(chv).lanes;
   const int tid = threadIdx.x;
   const int ll = tid / tpr;
   const int cl = tid - ll * tpr;
@@ -477,83 +420,50 @@ __global__ __launch_bounds__(256) void gn_apply_wino43_kernel(const float* __res
   const int n = blockIdx.y;
   const int l0 = blockIdx.x * lines_per_block;
   const int l1 = min(lines, l0 + lines_per_block);
-  const int w4n = w >> 2;
+  const int wtn = (int)((unsigned)w / VAR);      // tiles per line (w > 0: a shift)
   const float* xb = x + (int64_t)n * lines * w * ldx;
-  const int64_t vrow0 = (int64_t)n * lines * w4n;
+  const int64_t vrow0 = (int64_t)n * lines * wtn;
   const float* st = stats + (int64_t)n * groups * 2;
   float amax = 0.f;
   for (int cv = cl; cv < chv; cv += tpr) {
-    float gg[V], bb[V], mean[V], rstd[V];
-#pragma unroll
-    for (int k4 = 0; k4 < V / 4; ++k4) {
-      const float4 g = *reinterpret_cast<const float4*>(gamma + cv * V + 4 * k4);
-      const float4 b = *reinterpret_cast<const float4*>(beta + cv * V + 4 * k4);
-      gg[4 * k4] = g.x; gg[4 * k4 + 1] = g.y; gg[4 * k4 + 2] = g.z; gg[4 * k4 + 3] = g.w;
-      bb[4 * k4] = b.x; bb[4 * k4 + 1] = b.y; bb[4 * k4 + 2] = b.z; bb[4 * k4 + 3] = b.w;
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const int grp = (ch0 + cv * V + k) / cpg;
-      mean[k] = st[grp * 2];
-      rstd[k] = st[grp * 2 + 1];
-    }
-    auto actv = [&](const float* px, bool in, float (&o)[V]) {
-      if (!in) {
-#pragma unroll
-        for (int k = 0; k < V; ++k) o[k] = 0.f;
-        return;
-      }
-#pragma unroll
-      for (int k4 = 0; k4 < V / 4; ++k4) {
-        const float4 v = *reinterpret_cast<const float4*>(px + 4 * k4);
-        const float iv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          o[4 * k4 + k] = cs_act((iv[k] - mean[4 * k4 + k]) * rstd[4 * k4 + k] * gg[4 * k4 + k] + bb[4 * k4 + k], act) * a_scale;
-      }
-    };
+    const GnCols<V> cols(gamma, beta, st, ch0, cpg, cv * V);
     for (int line = l0 + ll; line < l1; line += linelanes) {
       const float* xl = xb + (int64_t)line * w * ldx + cv * V;
-      float d[6][V];
+      float d[VAR + 2][V];
 #pragma unroll
       for (int k = 0; k < V; ++k) d[0][k] = 0.f;
-      actv(xl, true, d[1]);
-      for (int t = 0; t < w4n; ++t) {
+      cols.norm_scaled(xl, act, a_scale, d[1]);
+      for (int t = 0; t < wtn; ++t) {
 #pragma unroll
-        for (int j = 2; j < 6; ++j) {
-          const int wi = 4 * t - 1 + j;
-          actv(xl + (int64_t)wi * ldx, wi < w, d[j]);
-        }
-        const int64_t off = (vrow0 + (int64_t)line * w4n + t) * ldv + cv * V;
+        for (int j = 2; j < VAR + 2; ++j) {
+          const int wi = VAR * t - 1 + j;
+          if (j <= VAR || wi < w) {
+            cols.norm_scaled(xl + (int64_t)wi * ldx, act, a_scale, d[j]);
+          } else {
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
-          hv hi, lo;
-#pragma unroll
-          for (int k = 0; k < V; ++k) {
-            float o;
-            if (q == 0) o = 4.f * d[0][k] - 5.f * d[2][k] + d[4][k];
-            else if (q == 1) o = (d[4][k] + d[3][k]) - 4.f * (d[1][k] + d[2][k]);
-            else if (q == 2) o = 4.f * (d[1][k] - d[2][k]) + (d[4][k] - d[3][k]);
-            else if (q == 3) o = 2.f * (d[3][k] - d[1][k]) + (d[4][k] - d[2][k]);
-            else if (q == 4) o = 2.f * (d[1][k] - d[3][k]) + (d[4][k] - d[2][k]);
-            else o = 4.f * d[1][k] - 5.f * d[3][k] + d[5][k];
-            amax = fmaxf(amax, fabsf(o));
-            const _Float16 hh = (_Float16)o;
-            hi[k] = hh;
-            lo[k] = (_Float16)(o - (float)hh);
+            for (int k = 0; k < V; ++k) d[j][k] = 0.f;
           }
-          *reinterpret_cast<hv*>(vh + q * pos_stride + off) = hi;
-          *reinterpret_cast<hv*>(vl + q * pos_stride + off) = lo;
+        }
+        const int64_t off = (vrow0 + (int64_t)line * wtn + t) * ldv + cv * V;
+#pragma unroll
+        for (int q = 0; q < VAR + 2; ++q) {
+          float o[V];
+#pragma unroll
+          for (int k = 0; k < V; ++k) o[k] = gn_wino_bt<VAR, V>(d, q, k);
+          cs_hv<V> hi, lo;
+          cs_pair_split<V>(o, hi, lo, amax);
+          *reinterpret_cast<cs_hv<V>*>(vh + q * pos_stride + off) = hi;
+          *reinterpret_cast<cs_hv<V>*>(vl + q * pos_stride + off) = lo;
         }
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-          d[0][k] = d[4][k];
-          d[1][k] = d[5][k];
+          d[0][k] = d[VAR][k];
+          d[1][k] = d[VAR + 1][k];
         }
       }
     }
   }
-  if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_amax_flag(status, amax);
 }
 
 // LayerNorm: one wave per row; each lane owns up to MAXV float4 chunks (c <= 64*4*MAXV).
@@ -568,26 +478,9 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x,
   const int ch4 = c >> 2;
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < m; row += (int64_t)gridDim.x * 4) {
     float4 v[MAXV];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      const int c4 = lane + 64 * k;
-      v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c4 < ch4) v[k] = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
-      s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-    }
-    const float mean = wave_sum(s) / (float)c;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      const int c4 = lane + 64 * k;
-      if (c4 < ch4) {
-        const float a = v[k].x - mean, b = v[k].y - mean, cc = v[k].z - mean, d = v[k].w - mean;
-        q += (a * a + b * b) + (cc * cc + d * d);
-      }
-    }
-    const float var = wave_sum(q) / (float)c;
-    const float rstd = 1.0f / sqrtf(var + eps);
+    const float s = cs_ln_load_row<MAXV>(x, row, ldx, lane, ch4, v);
+    float mean, rstd;
+    cs_ln_row_stats<MAXV>(v, s, lane, ch4, c, eps, mean, rstd);
 #pragma unroll
     for (int k = 0; k < MAXV; ++k) {
       const int c4 = lane + 64 * k;
@@ -619,63 +512,17 @@ __global__ __launch_bounds__(256) void ln_pair_kernel(const float* __restrict__ 
   float amax = 0.f;
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < m; row += (int64_t)gridDim.x * 4) {
     float4 v[MAXV];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {
-      const int c4 = lane + 64 * k;
-      v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c4 < ch4) v[k] = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
-      s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-    }
+    const float s = cs_ln_load_row<MAXV>(x, row, ldx, lane, ch4, v);
     amax = cs_ln_pair_row<MAXV>(v, s, lane, ch4, c, gamma, beta, y + row * (int64_t)ldy * 2, eps, a_scale, amax);
   }
-  if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_amax_flag(status, amax);
 }
 
-// Small tensors (one or two objects: a few MB, L2-resident): statistics and normalisation in ONE launch, one workgroup
-// per (sample, group).  The three-launch path costs ~23 us per GroupNorm there (6.8 + 4.6 + 11.5 us, each at its launch
-// floor), 61 times a step.  Threads walk the group's rows x cpg elements in a fixed stride, accumulate in fp64, and a
-// fixed LDS tree adds the 256 partials, so the statistics are reproducible; the second sweep re-reads the group from
-// L2 and applies the same expression as gn_apply_kernel.
-__global__ __launch_bounds__(256) void gn_small_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, float* __restrict__ y,
-                                                       float* __restrict__ stats, int rows, int c, int ldx, int ldy,
-                                                       int groups, float eps, int act) {
+// What the two one-launch kernels share: a workgroup of 256 per (sample, group), or per row share of one.
+// The fixed LDS tree over the workgroup's 256 (s, q): every thread leaves with the totals, so they are reproducible.
+__device__ __forceinline__ void gn_block_sum(double& s, double& q) {
   __shared__ double red[2][256];
-  const int n = blockIdx.x / groups, g = blockIdx.x - n * groups;
-  const int cpg = c / groups;
   const int tid = threadIdx.x;
-  const float* xb = x + (int64_t)n * rows * ldx + g * cpg;
-  float* yb = y + (int64_t)n * rows * ldy + g * cpg;
-  const int dr = 256 / cpg, dk = 256 - dr * cpg;          // element index + 256  ->  (row + dr, k + dk) with carry
-  auto next = [&](int& r, int& k) {
-    r += dr;
-    k += dk;
-    if (k >= cpg) {
-      k -= cpg;
-      ++r;
-    }
-  };
-  double s = 0, q = 0;
-  {
-    int r = tid / cpg, k = tid - r * cpg;
-    while (r < rows) {                                      // four loads in flight, accumulated in element order
-      float v[4];
-      int rr[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        rr[u] = r;
-        v[u] = r < rows ? xb[(int64_t)r * ldx + k] : 0.f;
-        next(r, k);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (rr[u] < rows) {
-          s += v[u];
-          q += (double)v[u] * v[u];
-        }
-    }
-  }
   red[0][tid] = s;
   red[1][tid] = q;
   __syncthreads();
@@ -687,37 +534,94 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const float* __restrict__
     }
     __syncthreads();
   }
-  const double count = (double)rows * cpg;
-  const double mean_d = red[0][0] / count;
-  double var = red[1][0] / count - mean_d * mean_d;
-  if (var < 0) var = 0;
+  s = red[0][0];
+  q = red[1][0];
+}
+// The walk over a group's rows x cpg elements, 256 apart: element index + 256  ->  (row + dr, k + dk) with carry
+struct GnWalk {
+  int cpg, dr, dk;
+  __device__ __forceinline__ explicit GnWalk(int cpg_) : cpg(cpg_), dr(256 / cpg_), dk(256 - dr * cpg_) {}
+  __device__ __forceinline__ void next(int& r, int& k) const {
+    r += dr;
+    k += dk;
+    if (k >= cpg) {
+      k -= cpg;
+      ++r;
+    }
+  }
+};
+// The apply sweep over rows [rbeg, rend) of the group at xb / yb (gamma, beta at the group's first channel): four loads in
+// flight, the same expression as gn_apply_kernel
+__device__ __forceinline__ void gn_small_apply(const float* __restrict__ xb, float* __restrict__ yb,
+                                               const float* __restrict__ gamma, const float* __restrict__ beta, int rbeg,
+                                               int rend, const GnWalk wk, int ldx, int ldy, float mean, float rstd, int act) {
+  const int tid = threadIdx.x;
+  int r = rbeg + tid / wk.cpg, k = tid - (tid / wk.cpg) * wk.cpg;
+  while (r < rend) {
+    float v[4], ga[4], be[4];
+    int rr[4], kk[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      rr[u] = r;
+      kk[u] = k;
+      if (r < rend) {
+        v[u] = xb[(int64_t)r * ldx + k];
+        ga[u] = gamma[k];
+        be[u] = beta[k];
+      }
+      wk.next(r, k);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (rr[u] < rend) yb[(int64_t)rr[u] * ldy + kk[u]] = cs_act((v[u] - mean) * rstd * ga[u] + be[u], act);
+  }
+}
+
+// Small tensors (one or two objects: a few MB, L2-resident): statistics and normalisation in ONE launch, one workgroup
+// per (sample, group).  The three-launch path costs ~23 us per GroupNorm there (6.8 + 4.6 + 11.5 us, each at its launch
+// floor), 61 times a step.  Threads walk the group's rows x cpg elements in a fixed stride, accumulate in fp64, and a
+// fixed LDS tree adds the 256 partials, so the statistics are reproducible; the second sweep re-reads the group from
+// L2 and applies the same expression as gn_apply_kernel.
+__global__ __launch_bounds__(256) void gn_small_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float* __restrict__ y,
+                                                       float* __restrict__ stats, int rows, int c, int ldx, int ldy,
+                                                       int groups, float eps, int act) {
+  const int n = blockIdx.x / groups, g = blockIdx.x - n * groups;
+  const int cpg = c / groups;
+  const int tid = threadIdx.x;
+  const float* xb = x + (int64_t)n * rows * ldx + g * cpg;
+  float* yb = y + (int64_t)n * rows * ldy + g * cpg;
+  const GnWalk wk(cpg);
+  double s = 0, q = 0;
+  {
+    int r = tid / cpg, k = tid - r * cpg;
+    while (r < rows) {                                      // four loads in flight, accumulated in element order
+      float v[4];
+      int rr[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        rr[u] = r;
+        v[u] = r < rows ? xb[(int64_t)r * ldx + k] : 0.f;
+        wk.next(r, k);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (rr[u] < rows) {
+          s += v[u];
+          q += (double)v[u] * v[u];
+        }
+    }
+  }
+  gn_block_sum(s, q);
+  double mean_d, var;
+  float rstd;
+  gn_moments(s, q, (double)rows * cpg, eps, mean_d, var, rstd);
   const float mean = (float)mean_d;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   if (tid == 0 && stats) {
     stats[2 * blockIdx.x] = mean;
     stats[2 * blockIdx.x + 1] = rstd;
   }
-  {
-    int r = tid / cpg, k = tid - r * cpg;
-    while (r < rows) {
-      float v[4], ga[4], be[4];
-      int rr[4], kk[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        rr[u] = r;
-        kk[u] = k;
-        if (r < rows) {
-          v[u] = xb[(int64_t)r * ldx + k];
-          ga[u] = gamma[g * cpg + k];
-          be[u] = beta[g * cpg + k];
-        }
-        next(r, k);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (rr[u] < rows) yb[(int64_t)rr[u] * ldy + kk[u]] = cs_act((v[u] - mean) * rstd * ga[u] + be[u], act);
-    }
-  }
+  gn_small_apply(xb, yb, gamma + g * cpg, beta + g * cpg, 0, rows, wk, ldx, ldy, mean, rstd, act);
 }
 
 // gn_small_kernel with the statistics taken from the producers' partials (r4): one workgroup per (sample, group) adds the
@@ -731,30 +635,18 @@ __global__ __launch_bounds__(256) void gn_small_parts_kernel(const float* __rest
                                                              int rsplit) {
   // r5: `rsplit` workgroups per (sample, group), each deriving the SAME statistics from the partials (a few hundred pairs)
   // and sweeping its share of the rows -- one or two objects are 64 (sample, group)s, a quarter of the CUs
-  __shared__ double red[2][256];
   const int sgi = blockIdx.x / rsplit, rs = blockIdx.x - sgi * rsplit;
   const int n = sgi / groups, g = sgi - n * groups;
   const int cpg = c / groups;
   const int tid = threadIdx.x;
   double s, q;
   gn_group_parts(sg, n, g, cpg, tid, 256, s, q);
-  red[0][tid] = s;
-  red[1][tid] = q;
-  __syncthreads();
-#pragma unroll
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) {
-      red[0][tid] += red[0][tid + o];
-      red[1][tid] += red[1][tid + o];
-    }
-    __syncthreads();
-  }
+  gn_block_sum(s, q);
   const double count = (double)rows * cpg;
-  const double mean_d = red[0][0] / count;
-  double var = red[1][0] / count - mean_d * mean_d;
-  if (var < 0) var = 0;
+  double mean_d, var;
+  float rstd;
+  gn_moments(s, q, count, eps, mean_d, var, rstd);
   const float mean = (float)mean_d;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   if (tid == 0 && stats && rs == 0) {
     stats[2 * sgi] = mean;
     stats[2 * sgi + 1] = rstd;
@@ -762,34 +654,8 @@ __global__ __launch_bounds__(256) void gn_small_parts_kernel(const float* __rest
   if (tid == 0 && bound && rs == 0) gn_bound_max(bound, mean_d, var, count);
   const int rper = (rows + rsplit - 1) / rsplit;
   const int rbeg = rs * rper, rend = min(rows, rbeg + rper);
-  const float* xb = x + (int64_t)n * rows * ldx + g * cpg;
-  float* yb = y + (int64_t)n * rows * ldy + g * cpg;
-  const int dr = 256 / cpg, dk = 256 - dr * cpg;
-  int r = rbeg + tid / cpg, k = tid - (tid / cpg) * cpg;
-  rows = rend;                                    // (this workgroup's share ends here; xb / yb were formed above)
-  while (r < rows) {
-    float v[4], ga[4], be[4];
-    int rr[4], kk[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      rr[u] = r;
-      kk[u] = k;
-      if (r < rows) {
-        v[u] = xb[(int64_t)r * ldx + k];
-        ga[u] = gamma[g * cpg + k];
-        be[u] = beta[g * cpg + k];
-      }
-      r += dr;
-      k += dk;
-      if (k >= cpg) {
-        k -= cpg;
-        ++r;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (rr[u] < rows) yb[(int64_t)rr[u] * ldy + kk[u]] = cs_act((v[u] - mean) * rstd * ga[u] + be[u], act);
-  }
+  gn_small_apply(x + (int64_t)n * rows * ldx + g * cpg, y + (int64_t)n * rows * ldy + g * cpg, gamma + g * cpg,
+                 beta + g * cpg, rbeg, rend, GnWalk(cpg), ldx, ldy, mean, rstd, act);
 }
 
 // row slices per sample: enough workgroups to fill the chip (~2048 in total) but no slice shorter than
@@ -800,6 +666,44 @@ int gn_nsplit(int rows, int nb) {
   if (n > cap) n = cap;
   if (n < 1) n = 1;
   return n < GN_MAX_SPLITS ? n : GN_MAX_SPLITS;
+}
+
+// rows per workgroup of gn_apply_kernel / gn_apply_split16_kernel: enough workgroups to fill the chip (>= ~2048 in total), each with at least 16 rows
+// per row-lane
+int gn_rows_per_block(int nb, int rows, int rowlanes) {
+  int blocks_per_sample = (2048 + nb - 1) / nb;
+  // (r5: down to four rows per row-lane -- one round of the kernel's four loads in flight -- where sixteen would leave
+  // most of the chip idle: 8192 x 224 at one object ran 128 workgroups x 4 dependent rounds, 12 us for 14 MB)
+  const int min_rows = (int64_t)nb * ((rows + 16 * rowlanes - 1) / (16 * rowlanes)) >= 1024 ? 16 : 4;
+  const int max_blocks = (rows + min_rows * rowlanes - 1) / (min_rows * rowlanes);
+  if (blocks_per_sample > max_blocks) blocks_per_sample = max_blocks;
+  if (blocks_per_sample < 1) blocks_per_sample = 1;
+  return (rows + blocks_per_sample - 1) / blocks_per_sample;
+}
+
+// one launch (gn_small_kernel / gn_small_parts_kernel) while the tensor is a few MB (it stays in L2 between the two sweeps)
+// and a group is a handful of elements per thread; otherwise statistics + apply
+bool gn_one_launch(int nb, int rows, int c, int groups) {
+  const int cpg = c / groups;
+  const int64_t small_group = cs_debug()->gn_small_group;      // (CS_GN_SMALL_GROUP: tuning override, tools/gn_bench.py)
+  return (int64_t)nb * rows * c * 4 <= GN_SMALL_BYTES && cpg <= 256 && (int64_t)rows * cpg <= small_group &&
+         (int64_t)nb * groups <= 65535;
+}
+
+// What the three channel-range apply entries ask of their arguments (`rows` = any of the row-count arguments already folded
+// by the caller: all must be positive).  The fp32 form has float4 accesses only (cgran = ldgran = 4, y1 = y0, no scale); the
+// pair forms store eight-byte halves of 8-channel operand rows (8, 8) and scale by a_scale > 0.
+bool gn_apply_args_ok(const void* x, const void* stats, const void* gamma, const void* beta, const void* y0,
+                      const void* y1, int nb, int c, int ldx, int ldy, int groups, int cpg, int ch0, int cgran,
+                      int ldgran, bool scaled, float a_scale) {
+  if (!x || !stats || !gamma || !beta || !y0 || !y1 || nb <= 0 || nb > 65535 || c <= 0 || groups <= 0 || cpg <= 0 ||
+      ch0 < 0)
+    return false;
+  if ((c & (cgran - 1)) || (ldx & 3) || (ldy & (ldgran - 1)) || ldx < c || ldy < c ||
+      (int64_t)ch0 + c > (int64_t)groups * cpg || (scaled && !(a_scale > 0.f)))
+    return false;
+  return !(((uintptr_t)x & 15) || ((uintptr_t)y0 & 15) || ((uintptr_t)y1 & 15) || ((uintptr_t)gamma & 15) ||
+           ((uintptr_t)beta & 15));
 }
 
 }  // namespace
@@ -864,9 +768,7 @@ extern "C" int cs_groupnorm_parts(const float* x, const CsGnSeg* segs, int nseg,
   const int rc0 = gn_pack_segs(segs, nseg, nb, c, sg);
   if (rc0 != CS_OK) return rc0;
   const int cpg = c / groups;
-  const int64_t small_group = cs_debug()->gn_small_group;
-  if ((int64_t)nb * rows * c * 4 <= GN_SMALL_BYTES && cpg <= 256 && (int64_t)rows * cpg <= small_group &&
-      (int64_t)nb * groups <= 65535) {
+  if (gn_one_launch(nb, rows, c, groups)) {
     // (row shares per (sample, group): up to four while the launch stays under ~512 workgroups and a share keeps >= 4
     // elements per thread; depends on the sample's own shape and on nb only through the workgroup budget -- the
     // arithmetic per element does not depend on it)
@@ -880,16 +782,32 @@ extern "C" int cs_groupnorm_parts(const float* x, const CsGnSeg* segs, int nseg,
   }
   // what cs_groupnorm_apply (float4 accesses) will ask for, checked BEFORE the finalize launch: a call that is turned down
   // has written nothing (c % 4 != 0 used to leave stats and bound behind and then return CS_EINVAL)
-  if ((c & 3) || (ldx & 3) || (ldy & 3) || nb > 65535 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) ||
-      ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15))
-    return CS_EINVAL;
+  if (!gn_apply_args_ok(x, stats, gamma, beta, y, y, nb, c, ldx, ldy, groups, cpg, 0, 4, 4, false, 0.f)) return CS_EINVAL;
   const int rc = cs_groupnorm_finalize_parts(segs, nseg, nb, rows, c, groups, eps, stats, bound, stream);
   if (rc) return rc;
   return cs_groupnorm_apply(x, stats, gamma, beta, y, nb, rows, c, ldx, ldy, groups, act, stream);
 }
 
 static int gn_stats_impl(const float* x, int nb, int rows, int c, int ldx, int groups, float eps, void* ws, float* stats,
-                         float* bound, cs_stream_t stream);
+                         float* bound, cs_stream_t stream) {
+  if (!x || !ws || !stats || nb <= 0 || rows <= 0 || c <= 0 || groups <= 0) return CS_EINVAL;
+  if ((c & 3) || (ldx & 3) || ldx < c || c % groups || groups > 256) return CS_EINVAL;
+  if (((uintptr_t)x & 15) || ((uintptr_t)ws & 7)) return CS_EINVAL;
+  const int nsplit = gn_nsplit(rows, nb);
+  const int rps = (rows + nsplit - 1) / nsplit;
+  const size_t smem = (size_t)gn_map(c >> 2).lanes * c * 2 * sizeof(double);
+  if (smem > 64 * 1024) return CS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  CS_LAUNCH(gn_partial_kernel, dim3((unsigned)(nb * nsplit)), dim3(256), smem, s, x, rows,
+                     c, ldx, groups, nsplit, rps, (double*)ws);
+  CS_CHECK_LAUNCH();
+  const int total = nb * groups;
+  CS_LAUNCH(gn_finalize_kernel, dim3((total + 3) / 4), dim3(256), 0, s,
+                     (const double*)ws, nsplit, groups, (double)rows * (c / groups), eps, stats,
+                     total, bound);
+  CS_CHECK_LAUNCH();
+  return CS_OK;
+}
 
 extern "C" int cs_groupnorm_stats(const float* x, int nb, int rows, int c, int ldx, int groups,
                                   float eps, void* ws, float* stats, cs_stream_t stream) {
@@ -904,55 +822,16 @@ extern "C" int cs_groupnorm_stats_bound(const float* x, int nb, int rows, int c,
   return gn_stats_impl(x, nb, rows, c, ldx, groups, eps, ws, stats, bound, stream);
 }
 
-static int gn_stats_impl(const float* x, int nb, int rows, int c, int ldx, int groups, float eps, void* ws, float* stats,
-                         float* bound, cs_stream_t stream) {
-  if (!x || !ws || !stats || nb <= 0 || rows <= 0 || c <= 0 || groups <= 0) return CS_EINVAL;
-  if ((c & 3) || (ldx & 3) || ldx < c || c % groups || groups > 256) return CS_EINVAL;
-  if (((uintptr_t)x & 15) || ((uintptr_t)ws & 7)) return CS_EINVAL;
-  const int nsplit = gn_nsplit(rows, nb);
-  const int rps = (rows + nsplit - 1) / nsplit;
-  const int ch4 = c >> 2;
-  const int tpr = ch4 < 256 ? ch4 : 256;
-  const int rowlanes = 256 / tpr;
-  const size_t smem = (size_t)rowlanes * c * 2 * sizeof(double);
-  if (smem > 64 * 1024) return CS_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  CS_LAUNCH(gn_partial_kernel, dim3((unsigned)(nb * nsplit)), dim3(256), smem, s, x, rows,
-                     c, ldx, groups, nsplit, rps, (double*)ws);
-  CS_CHECK_LAUNCH();
-  const int total = nb * groups;
-  CS_LAUNCH(gn_finalize_kernel, dim3((total + 3) / 4), dim3(256), 0, s,
-                     (const double*)ws, nsplit, groups, (double)rows * (c / groups), eps, stats,
-                     total, bound);
-  CS_CHECK_LAUNCH();
-  return CS_OK;
-}
-
-// Channel-range form of the two apply entries: the c channels handled are channels ch0 .. ch0 + c of a tensor that was
+// Channel-range form of the apply entries: the c channels handled are channels ch0 .. ch0 + c of a tensor that was
 // normalised over `groups` groups of `cpg` channels each (stats: [nb][groups][2]); x, gamma, beta and y point AT channel
 // ch0.  Lets one statistics pass over a concatenated tensor [h | skip] feed two separate operand tensors (the channel
 // split of the classifier-free-guidance output blocks, unet.py::_res_split).
 extern "C" int cs_groupnorm_apply_range(const float* x, const float* stats, const float* gamma, const float* beta,
                                         float* y, int nb, int rows, int c, int ldx, int ldy, int groups, int cpg,
                                         int ch0, int act, cs_stream_t stream) {
-  if (!x || !stats || !gamma || !beta || !y || nb <= 0 || rows <= 0 || c <= 0 || groups <= 0 || cpg <= 0 || ch0 < 0)
+  if (rows <= 0 || !gn_apply_args_ok(x, stats, gamma, beta, y, y, nb, c, ldx, ldy, groups, cpg, ch0, 4, 4, false, 0.f))
     return CS_EINVAL;
-  if ((c & 3) || (ldx & 3) || (ldy & 3) || ldx < c || ldy < c || (int64_t)ch0 + c > (int64_t)groups * cpg) return CS_EINVAL;
-  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)gamma & 15) ||
-      ((uintptr_t)beta & 15))
-    return CS_EINVAL;
-  if (nb > 65535) return CS_EINVAL;
-  // enough workgroups to fill the chip (>= ~2048 in total), each with at least 16 rows per row-lane
-  const int ch4 = c >> 2;
-  const int rowlanes = 256 / (ch4 < 256 ? ch4 : 256);
-  int blocks_per_sample = (2048 + nb - 1) / nb;
-  // (r5: down to four rows per row-lane -- one round of the kernel's four loads in flight -- where sixteen would leave
-  // most of the chip idle: 8192 x 224 at one object ran 128 workgroups x 4 dependent rounds, 12 us for 14 MB)
-  const int min_rows = (int64_t)nb * ((rows + 16 * rowlanes - 1) / (16 * rowlanes)) >= 1024 ? 16 : 4;
-  const int max_blocks = (rows + min_rows * rowlanes - 1) / (min_rows * rowlanes);
-  if (blocks_per_sample > max_blocks) blocks_per_sample = max_blocks;
-  if (blocks_per_sample < 1) blocks_per_sample = 1;
-  const int rpb = (rows + blocks_per_sample - 1) / blocks_per_sample;
+  const int rpb = gn_rows_per_block(nb, rows, gn_map(c >> 2).lanes);
   CS_LAUNCH(gn_apply_kernel, dim3((unsigned)((rows + rpb - 1) / rpb), (unsigned)nb), dim3(256), 0,
             (hipStream_t)stream, x, stats, gamma, beta, y, rows, c, ldx, ldy, groups, act, rpb, cpg, ch0);
   CS_CHECK_LAUNCH();
@@ -970,26 +849,10 @@ extern "C" int cs_groupnorm_apply_split16_range(const float* x, const float* sta
                                                 const float* beta, void* y_hi, void* y_lo, int nb, int rows, int c,
                                                 int ldx, int ldy, int groups, int cpg, int ch0, int act, float a_scale,
                                                 int32_t* status, cs_stream_t stream) {
-  if (!x || !stats || !gamma || !beta || !y_hi || !y_lo || nb <= 0 || rows <= 0 || c <= 0 || groups <= 0 || cpg <= 0 ||
-      ch0 < 0)
+  if (rows <= 0 ||
+      !gn_apply_args_ok(x, stats, gamma, beta, y_hi, y_lo, nb, c, ldx, ldy, groups, cpg, ch0, 8, 8, true, a_scale))
     return CS_EINVAL;
-  if ((c & 7) || (ldx & 3) || (ldy & 7) || ldx < c || ldy < c || (int64_t)ch0 + c > (int64_t)groups * cpg ||
-      !(a_scale > 0.f))
-    return CS_EINVAL;
-  if (((uintptr_t)x & 15) || ((uintptr_t)y_hi & 15) || ((uintptr_t)y_lo & 15) || ((uintptr_t)gamma & 15) ||
-      ((uintptr_t)beta & 15))
-    return CS_EINVAL;
-  if (nb > 65535) return CS_EINVAL;
-  const int ch4 = c >> 2;
-  const int rowlanes = 256 / (ch4 < 256 ? ch4 : 256);
-  int blocks_per_sample = (2048 + nb - 1) / nb;
-  // (r5: down to four rows per row-lane -- one round of the kernel's four loads in flight -- where sixteen would leave
-  // most of the chip idle: 8192 x 224 at one object ran 128 workgroups x 4 dependent rounds, 12 us for 14 MB)
-  const int min_rows = (int64_t)nb * ((rows + 16 * rowlanes - 1) / (16 * rowlanes)) >= 1024 ? 16 : 4;
-  const int max_blocks = (rows + min_rows * rowlanes - 1) / (min_rows * rowlanes);
-  if (blocks_per_sample > max_blocks) blocks_per_sample = max_blocks;
-  if (blocks_per_sample < 1) blocks_per_sample = 1;
-  const int rpb = (rows + blocks_per_sample - 1) / blocks_per_sample;
+  const int rpb = gn_rows_per_block(nb, rows, gn_map(c >> 2).lanes);
   CS_LAUNCH(gn_apply_split16_kernel, dim3((unsigned)((rows + rpb - 1) / rpb), (unsigned)nb), dim3(256), 0,
             (hipStream_t)stream, x, stats, gamma, beta, (_Float16*)y_hi, (_Float16*)y_lo, rows, c, ldx, ldy, groups, act,
             a_scale, rpb, status, cpg, ch0);
@@ -1001,14 +864,8 @@ extern "C" int cs_groupnorm_apply_wino_range(const float* x, const float* stats,
                                              void* v_hi, void* v_lo, int nb, int d, int h, int w, int c, int ldx, int ldv,
                                              int groups, int cpg, int ch0, int act, float a_scale, int variant,
                                              int32_t* status, cs_stream_t stream) {
-  if (!x || !stats || !gamma || !beta || !v_hi || !v_lo || nb <= 0 || d <= 0 || h <= 0 || w < 2 || c <= 0 || groups <= 0 ||
-      cpg <= 0 || ch0 < 0 || (variant != 2 && variant != 4))
-    return CS_EINVAL;
-  if ((w % variant) || (c & 7) || (int64_t)ch0 + c > (int64_t)groups * cpg || (ldx & 3) || (ldv & 7) || ldx < c || ldv < c ||
-      !(a_scale > 0.f) || nb > 65535)
-    return CS_EINVAL;
-  if (((uintptr_t)x & 15) || ((uintptr_t)v_hi & 15) || ((uintptr_t)v_lo & 15) || ((uintptr_t)gamma & 15) ||
-      ((uintptr_t)beta & 15))
+  if (d <= 0 || h <= 0 || w < 2 || (variant != 2 && variant != 4) || (w % variant) ||
+      !gn_apply_args_ok(x, stats, gamma, beta, v_hi, v_lo, nb, c, ldx, ldv, groups, cpg, ch0, 8, 8, true, a_scale))
     return CS_EINVAL;
   const int64_t lines64 = (int64_t)d * h;
   if (lines64 * w > 0x7fffffffLL) return CS_EINVAL;
@@ -1018,8 +875,7 @@ extern "C" int cs_groupnorm_apply_wino_range(const float* x, const float* stats,
 #else
   constexpr int WV = 4;            // channels per thread of the F(4,3) kernel
 #endif
-  const int ch4 = variant == 4 ? c / WV : c >> 2;
-  const int linelanes = 256 / (ch4 < 256 ? ch4 : 256);
+  const int linelanes = gn_map(variant == 4 ? c / WV : c >> 2).lanes;
   // ~2048 workgroups in all, at least one line per line-lane
   int blocks_per_sample = (2048 + nb - 1) / nb;
   const int max_blocks = (lines + linelanes - 1) / linelanes;
@@ -1028,11 +884,11 @@ extern "C" int cs_groupnorm_apply_wino_range(const float* x, const float* stats,
   const int lpb = (lines + blocks_per_sample - 1) / blocks_per_sample;
   const int64_t pos_stride = (int64_t)nb * lines * (w / variant) * ldv;
   if (variant == 4) {
-    CS_LAUNCH(gn_apply_wino43_kernel<WV>, dim3((unsigned)((lines + lpb - 1) / lpb), (unsigned)nb), dim3(256), 0,
+    CS_LAUNCH((gn_apply_wino_kernel<4, WV>), dim3((unsigned)((lines + lpb - 1) / lpb), (unsigned)nb), dim3(256), 0,
               (hipStream_t)stream, x, stats, gamma, beta, (_Float16*)v_hi, (_Float16*)v_lo, lines, w, c, ldx, ldv, groups, act,
               a_scale, lpb, pos_stride, status, cpg, ch0);
   } else {
-    CS_LAUNCH(gn_apply_wino16_kernel, dim3((unsigned)((lines + lpb - 1) / lpb), (unsigned)nb), dim3(256), 0,
+    CS_LAUNCH((gn_apply_wino_kernel<2, 4>), dim3((unsigned)((lines + lpb - 1) / lpb), (unsigned)nb), dim3(256), 0,
               (hipStream_t)stream, x, stats, gamma, beta, (_Float16*)v_hi, (_Float16*)v_lo, lines, w, c, ldx, ldv, groups, act,
               a_scale, lpb, pos_stride, status, cpg, ch0);
   }
@@ -1070,12 +926,7 @@ extern "C" int cs_groupnorm(const float* x, const float* gamma, const float* bet
                             cs_stream_t stream) {
   if (!x || !gamma || !beta || !y || !stats || nb <= 0 || rows <= 0 || c <= 0 || groups <= 0) return CS_EINVAL;
   if (c % groups || ldx < c || ldy < c) return CS_EINVAL;
-  const int cpg = c / groups;
-  const int64_t small_group = cs_debug()->gn_small_group;      // (CS_GN_SMALL_GROUP: tuning override, tools/gn_bench.py)
-  // one launch while the tensor is a few MB (it stays in L2 between the two sweeps) and a group is a handful of
-  // elements per thread; otherwise statistics (two launches) + apply
-  if ((int64_t)nb * rows * c * 4 <= GN_SMALL_BYTES && cpg <= 256 && (int64_t)rows * cpg <= small_group &&
-      (int64_t)nb * groups <= 65535) {
+  if (gn_one_launch(nb, rows, c, groups)) {
     CS_LAUNCH(gn_small_kernel, dim3((unsigned)(nb * groups)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
               stats, rows, c, ldx, ldy, groups, eps, act);
     CS_CHECK_LAUNCH();
@@ -1100,17 +951,8 @@ extern "C" int cs_layernorm(const float* x, const float* gamma, const float* bet
   if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)gamma & 15) ||
       ((uintptr_t)beta & 15))
     return CS_EINVAL;
-  const int ch4 = c >> 2;
   const int grid = cs_grid_for(((int64_t)m + 3) / 4, 1, 256 * 32);
-  hipStream_t s = (hipStream_t)stream;
-  if (ch4 <= 64 * 2)
-    CS_LAUNCH(ln_kernel<2>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, m, c, ldx, ldy, eps);
-  else if (ch4 <= 64 * 4)
-    CS_LAUNCH(ln_kernel<4>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, m, c, ldx, ldy, eps);
-  else if (ch4 <= 64 * 8)
-    CS_LAUNCH(ln_kernel<8>, dim3(grid), dim3(256), 0, s, x, gamma, beta, y, m, c, ldx, ldy, eps);
-  else
-    return CS_EINVAL;
+  CS_LN_LAUNCH(ln_kernel, c >> 2, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, m, c, ldx, ldy, eps);
   CS_CHECK_LAUNCH();
   return CS_OK;
 }
@@ -1122,18 +964,9 @@ extern "C" int cs_layernorm_pair16(const float* x, const float* gamma, const flo
   if (!x || !gamma || !beta || !y || m <= 0 || c <= 0 || !(a_scale > 0.f)) return CS_EINVAL;
   if ((c & 15) || (ldx & 3) || (ldy & 15) || ldx < c || ldy < c) return CS_EINVAL;
   if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15)) return CS_EINVAL;
-  const int ch4 = c >> 2;
   const int grid = cs_grid_for(((int64_t)m + 3) / 4, 1, 256 * 32);
-  hipStream_t s = (hipStream_t)stream;
-  _Float16* yo = (_Float16*)y;
-  if (ch4 <= 64 * 2)
-    CS_LAUNCH(ln_pair_kernel<2>, dim3(grid), dim3(256), 0, s, x, gamma, beta, yo, m, c, ldx, ldy, eps, a_scale, status);
-  else if (ch4 <= 64 * 4)
-    CS_LAUNCH(ln_pair_kernel<4>, dim3(grid), dim3(256), 0, s, x, gamma, beta, yo, m, c, ldx, ldy, eps, a_scale, status);
-  else if (ch4 <= 64 * 8)
-    CS_LAUNCH(ln_pair_kernel<8>, dim3(grid), dim3(256), 0, s, x, gamma, beta, yo, m, c, ldx, ldy, eps, a_scale, status);
-  else
-    return CS_EINVAL;
+  CS_LN_LAUNCH(ln_pair_kernel, c >> 2, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (_Float16*)y, m, c, ldx,
+               ldy, eps, a_scale, status);
   CS_CHECK_LAUNCH();
   return CS_OK;
 }

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void twin_ln_pair_kernel(const float* __restri
       amax = cs_ln_pair_row<MAXV>(v, s, lane, ch4, c, gamma, beta, pair + orow * (int64_t)ldp * 2, eps, a_scale, amax);
     }
   }
-  if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
+  cs_pair_amax_flag(status, amax);
 }
 
 }  // namespace
@@ -76,21 +76,9 @@ extern "C" int cs_twin_layernorm_pair16(const float* y, const float* rowvec, con
   if (((uintptr_t)y & 15) || ((uintptr_t)rowvec & 15) || ((uintptr_t)res & 15) || ((uintptr_t)gamma & 15) ||
       ((uintptr_t)beta & 15) || ((uintptr_t)t1 & 15) || ((uintptr_t)pair & 15))
     return CS_EINVAL;
-  const int ch4 = c >> 2;
   const int grid = cs_grid_for(((int64_t)m + 3) / 4, 1, 256 * 32);
-  hipStream_t s = (hipStream_t)stream;
-  _Float16* po = (_Float16*)pair;
-  if (ch4 <= 64 * 2)
-    CS_LAUNCH(twin_ln_pair_kernel<2>, dim3(grid), dim3(256), 0, s, y, rowvec, res, gamma, beta, t1, po, m, c, ldy, ldrv, rv_rows,
-              ldr, ldt, ldp, eps, a_scale, status);
-  else if (ch4 <= 64 * 4)
-    CS_LAUNCH(twin_ln_pair_kernel<4>, dim3(grid), dim3(256), 0, s, y, rowvec, res, gamma, beta, t1, po, m, c, ldy, ldrv, rv_rows,
-              ldr, ldt, ldp, eps, a_scale, status);
-  else if (ch4 <= 64 * 8)
-    CS_LAUNCH(twin_ln_pair_kernel<8>, dim3(grid), dim3(256), 0, s, y, rowvec, res, gamma, beta, t1, po, m, c, ldy, ldrv, rv_rows,
-              ldr, ldt, ldp, eps, a_scale, status);
-  else
-    return CS_EINVAL;
+  CS_LN_LAUNCH(twin_ln_pair_kernel, c >> 2, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, rowvec, res, gamma, beta, t1,
+               (_Float16*)pair, m, c, ldy, ldrv, rv_rows, ldr, ldt, ldp, eps, a_scale, status);
   CS_CHECK_LAUNCH();
   return CS_OK;
 }

@@ -951,6 +951,89 @@ class Pair16:
 # Switches: CsDebug.no_split16 / split16_min_rows (CS_NO_SPLIT16, CS_SPLIT16_MIN_ROWS).
 
 
+def _gn_form(x: Tensor, c: int, split16, wino, who: str) -> int:
+    """The output form of a GroupNorm apply: 0 = fp32, 1 = Split16, 2 / 4 = Wino16 F(2,3) / F(4,3) (wino: the variant
+    wants_wino returned -- 2 / True or 4).  The pre-split forms exist only under SPLIT16_PRODUCERS: fp32 otherwise."""
+    if not _sw("SPLIT16_PRODUCERS"):
+        return 0
+    if not wino:
+        return 1 if split16 else 0
+    v = 4 if wino == 4 else 2
+    if x.dim() != 5 or int(x.shape[3]) % v or c % 8:
+        raise L.CsError(f"{who}(wino=v) needs x as [nb, d, h, w, c] with w % v == 0 and c % 8 == 0")
+    return v
+
+
+def _gn_out(x: Tensor, out: Optional[Tensor]):
+    """(out, ldy) of an fp32 GroupNorm output: allocated like x when not given"""
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    om, oc, ldy = rows_ld(out, "out")
+    if (om, oc) != rows_ld(x, "x")[:2]:
+        raise L.CsError("groupnorm out shape mismatch")
+    return out, ldy
+
+
+def _gn_stats(x: Tensor, groups: int, eps: float, bound: Optional[Tensor]) -> Tensor:
+    """(mean, rstd) [nb, groups, 2] of x (the native driver's gn_stats_run): from its producers' partials when x carries them
+    (cs_groupnorm_finalize_parts: no pass over the tensor), else by a statistics pass -- cs_groupnorm_stats_bound when a
+    bound is wanted, cs_groupnorm_stats otherwise.  bound: a zeroed 1-element slot, used under DYN_SCALE only; it receives
+    x's magnitude bound and x remembers it (`x.cs_bound`)."""
+    nb = x.shape[0]
+    m, c, ldx = rows_ld(x, "x")
+    if not _sw("DYN_SCALE"):
+        bound = None
+    segs = stats_segments(x)
+    if segs is not None:
+        stats = groupnorm_stats_from_parts(segs, nb, m // nb, c, groups, eps, x.device, bound)
+    else:
+        lib = L.load()
+        ws = torch.empty(lib.cs_groupnorm_ws_bytes(nb, groups) // 8, dtype=torch.float64, device=x.device)
+        stats = torch.empty((nb, groups, 2), dtype=torch.float32, device=x.device)
+        if bound is not None:       # no partials on x: the statistics pass leaves the magnitude bound beside (mean, rstd)
+            L.check(lib.cs_groupnorm_stats_bound(x.data_ptr(), nb, m // nb, c, ldx, groups, eps, ws.data_ptr(),
+                                                 stats.data_ptr(), bound.data_ptr(), _stream()), "cs_groupnorm_stats_bound")
+        else:
+            L.check(lib.cs_groupnorm_stats(x.data_ptr(), nb, m // nb, c, ldx, groups, eps, ws.data_ptr(), stats.data_ptr(),
+                                           _stream()), "cs_groupnorm_stats")
+    if bound is not None:
+        x.cs_bound = bound
+    return stats
+
+
+def _gn_emit(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, groups: int, act: int, form: int,
+             a_scale: Optional[float] = None, out: Optional[Tensor] = None, rng=None):
+    """Normalise + affine + activation of x under `stats` in the output form `form` (_gn_form), one library call (the native
+    driver's gn_emit).  rng = (cpg, ch0): x, gamma, beta hold channels ch0 .. ch0 + c of the normalised tensor (the _range
+    entries); None: the whole tensor.  Wino16 operands sit at a_scale / 2 (F(2,3)) resp. / 16 (F(4,3)): the transformed
+    values are bounded by 2 x resp. 10 x the activation's bound."""
+    nb = x.shape[0]
+    m, c, ldx = rows_ld(x, "x")
+    lib = L.load()
+    head = (x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr())
+    if form == 0:
+        out, ldy = _gn_out(x, out)
+        name = "cs_groupnorm_apply_range" if rng else "cs_groupnorm_apply"
+        L.check(getattr(lib, name)(*head, out.data_ptr(), nb, m // nb, c, ldx, ldy, groups, *(rng or ()), act, _stream()), name)
+        return out
+    a_sc = float(a_scale or A_SCALE) * {1: 1.0, 2: 0.5, 4: 0.0625}[form]
+    status = status_word(x.device).data_ptr()
+    if form == 1:
+        yh = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+        yl = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+        name = "cs_groupnorm_apply_split16_range" if rng else "cs_groupnorm_apply_split16"
+        L.check(getattr(lib, name)(*head, yh.data_ptr(), yl.data_ptr(), nb, m // nb, c, ldx, c, groups, *(rng or ()), act, a_sc,
+                                   status, _stream()), name)
+        return Split16(yh, yl, a_sc)
+    d_, h_, w_ = int(x.shape[1]), int(x.shape[2]), int(x.shape[3])
+    yh = torch.empty((form + 2, nb, d_, h_, w_ // form, c), dtype=torch.float16, device=x.device)
+    yl = torch.empty_like(yh)
+    L.check(lib.cs_groupnorm_apply_wino_range(*head, yh.data_ptr(), yl.data_ptr(), nb, d_, h_, w_, c, ldx, c, groups,
+                                              *(rng or (c // groups, 0)), act, a_sc, form, status, _stream()),
+            "cs_groupnorm_apply_wino_range")
+    return Wino16(yh, yl, a_sc, (nb, d_, h_, w_), form)
+
+
 def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, act: int = L.ACT_NONE,
               out: Optional[Tensor] = None, split16: bool = False, a_scale: Optional[float] = None,
               bound: Optional[Tensor] = None, wino: bool = False):
@@ -965,162 +1048,49 @@ def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, a
     nb = x.shape[0]
     m, c, ldx = rows_ld(x, "x")
     rows = m // nb
-    lib = L.load()
+    form = _gn_form(x, c, split16, wino, "groupnorm")
+    if not _sw("DYN_SCALE"):
+        bound = None
     segs = stats_segments(x)
-    # (wino: the variant wants_wino returned -- 2 / True = F(2,3), 4 = F(4,3); operand scale / 2 resp. / 16: the transformed
-    # values are bounded by 2 x resp. 10 x the activation's bound)
-    wino = (4 if wino == 4 else 2 if wino else 0) if _sw("SPLIT16_PRODUCERS") else 0
-    if wino:
-        if x.dim() != 5 or int(x.shape[3]) % wino or c % 8:
-            raise L.CsError("groupnorm(wino=v) needs x as [nb, d, h, w, c] with w % v == 0 and c % 8 == 0")
-        split16 = True          # (same statistics routes as the pre-split pair; only the apply kernel differs)
-
-    def _emit(stats):
-        yshape = (wino + 2, nb, int(x.shape[1]), int(x.shape[2]), int(x.shape[3]) // wino, c) if wino else x.shape
-        yh = torch.empty(yshape, dtype=torch.float16, device=x.device)
-        yl = torch.empty(yshape, dtype=torch.float16, device=x.device)
-        if wino:
-            a_sc = float(a_scale or A_SCALE) * (0.5 if wino == 2 else 0.0625)
-            L.check(lib.cs_groupnorm_apply_wino_range(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                      yh.data_ptr(), yl.data_ptr(), nb, int(x.shape[1]), int(x.shape[2]),
-                                                      int(x.shape[3]), c, ldx, c, groups, c // groups, 0, act, a_sc, wino,
-                                                      status_word(x.device).data_ptr(), _stream()),
-                    "cs_groupnorm_apply_wino_range")
-            return Wino16(yh, yl, a_sc, (nb, int(x.shape[1]), int(x.shape[2]), int(x.shape[3])), wino)
-        a_sc = float(a_scale or A_SCALE)
-        L.check(lib.cs_groupnorm_apply_split16(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                               yh.data_ptr(), yl.data_ptr(), nb, rows, c, ldx, c, groups, act,
-                                               a_sc, status_word(x.device).data_ptr(), _stream()),
-                "cs_groupnorm_apply_split16")
-        return Split16(yh, yl, a_sc)
-
-    if segs is not None and not (split16 and _sw("SPLIT16_PRODUCERS")):
-        # one call: a single launch for small tensors, finalize + apply otherwise (cs_groupnorm_parts decides)
-        if out is None:
-            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        om, oc, ldy = rows_ld(out, "out")
-        if om != m or oc != c:
-            raise L.CsError("groupnorm out shape mismatch")
-        stats = torch.empty((nb, groups, 2), dtype=torch.float32, device=x.device)
-        if not _sw("DYN_SCALE"):
-            bound = None
+    if form or (segs is None and bound is not None):
+        if not form:
+            out, _ = _gn_out(x, out)        # (a mismatch is reported before anything is launched)
+        return _gn_emit(x, _gn_stats(x, groups, eps, bound), gamma, beta, groups, act, form, a_scale, out)
+    # fp32 output in one call, a single launch for small tensors (one or two objects): the library decides
+    out, ldy = _gn_out(x, out)
+    lib = L.load()
+    stats = torch.empty((nb, groups, 2), dtype=torch.float32, device=x.device)
+    if segs is not None:        # ... finalize + apply otherwise
         L.check(lib.cs_groupnorm_parts(x.data_ptr(), _seg_array(segs), len(segs), gamma.data_ptr(), beta.data_ptr(),
                                        out.data_ptr(), nb, rows, c, ldx, ldy, groups, eps, act, stats.data_ptr(),
                                        _ptr(bound), _stream()), "cs_groupnorm_parts")
         if bound is not None:
             x.cs_bound = bound
-        return out
-    if segs is not None:
-        if not _sw("DYN_SCALE"):
-            bound = None
-        stats = groupnorm_stats_from_parts(segs, nb, rows, c, groups, eps, x.device, bound)
-        if bound is not None:
-            x.cs_bound = bound
-        if split16 and _sw("SPLIT16_PRODUCERS"):
-            return _emit(stats)
-        if out is None:
-            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        om, oc, ldy = rows_ld(out, "out")
-        if om != m or oc != c:
-            raise L.CsError("groupnorm out shape mismatch")
-        L.check(lib.cs_groupnorm_apply(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
-                                       nb, rows, c, ldx, ldy, groups, act, _stream()), "cs_groupnorm_apply")
-        return out
-    ws = torch.empty(lib.cs_groupnorm_ws_bytes(nb, groups) // 8, dtype=torch.float64, device=x.device)
-    stats = torch.empty((nb, groups, 2), dtype=torch.float32, device=x.device)
-    want_bound = bound is not None and _sw("DYN_SCALE")
-
-    def _stats():
-        if want_bound:      # no partials on x: the statistics pass leaves the magnitude bound beside (mean, rstd)
-            L.check(lib.cs_groupnorm_stats_bound(x.data_ptr(), nb, rows, c, ldx, groups, eps, ws.data_ptr(), stats.data_ptr(),
-                                                 bound.data_ptr(), _stream()), "cs_groupnorm_stats_bound")
-            x.cs_bound = bound
-        else:
-            L.check(lib.cs_groupnorm_stats(x.data_ptr(), nb, rows, c, ldx, groups, eps, ws.data_ptr(),
-                                           stats.data_ptr(), _stream()), "cs_groupnorm_stats")
-    if split16 and _sw("SPLIT16_PRODUCERS"):
-        _stats()
-        return _emit(stats)
-    if out is None:
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    om, oc, ldy = rows_ld(out, "out")
-    if om != m or oc != c:
-        raise L.CsError("groupnorm out shape mismatch")
-    if want_bound:
-        _stats()
-        L.check(lib.cs_groupnorm_apply(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
-                                       nb, rows, c, ldx, ldy, groups, act, _stream()), "cs_groupnorm_apply")
-        return out
-    # one launch for small tensors (one or two objects), statistics + apply otherwise: cs_groupnorm decides
-    L.check(lib.cs_groupnorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), nb, rows, c, ldx, ldy,
-                             groups, eps, act, ws.data_ptr(), stats.data_ptr(), _stream()), "cs_groupnorm")
+    else:                       # ... statistics + apply otherwise
+        ws = torch.empty(lib.cs_groupnorm_ws_bytes(nb, groups) // 8, dtype=torch.float64, device=x.device)
+        L.check(lib.cs_groupnorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), nb, rows, c, ldx, ldy,
+                                 groups, eps, act, ws.data_ptr(), stats.data_ptr(), _stream()), "cs_groupnorm")
     return out
 
 
 def groupnorm_stats(x: Tensor, groups: int, eps: float, bound: Optional[Tensor] = None) -> Tensor:
     """(mean, rstd) per (sample, group) of a channels-last tensor: [nb, groups, 2] fp32 (fp64 accumulation)."""
     _chk(x, "x")
-    nb = x.shape[0]
-    m, c, ldx = rows_ld(x, "x")
-    lib = L.load()
-    segs = stats_segments(x)
-    if segs is not None:
-        if bound is not None and _sw("DYN_SCALE"):
-            x.cs_bound = bound
-        else:
-            bound = None
-        return groupnorm_stats_from_parts(segs, nb, m // nb, c, groups, eps, x.device, bound)
-    ws = torch.empty(lib.cs_groupnorm_ws_bytes(nb, groups) // 8, dtype=torch.float64, device=x.device)
-    stats = torch.empty((nb, groups, 2), dtype=torch.float32, device=x.device)
-    if bound is not None and _sw("DYN_SCALE"):
-        L.check(lib.cs_groupnorm_stats_bound(x.data_ptr(), nb, m // nb, c, ldx, groups, eps, ws.data_ptr(), stats.data_ptr(),
-                                             bound.data_ptr(), _stream()), "cs_groupnorm_stats_bound")
-        x.cs_bound = bound
-        return stats
-    L.check(lib.cs_groupnorm_stats(x.data_ptr(), nb, m // nb, c, ldx, groups, eps, ws.data_ptr(), stats.data_ptr(),
-                                   _stream()), "cs_groupnorm_stats")
-    return stats
+    return _gn_stats(x, groups, eps, bound)
 
 
 def groupnorm_apply_range(x: Tensor, stats: Tensor, gamma: Tensor, beta: Tensor, cpg: int, ch0: int,
                           act: int = L.ACT_NONE, split16: bool = False, a_scale: Optional[float] = None, wino: bool = False):
     """Normalise + affine + activation of a CHANNEL RANGE: x (and gamma / beta) hold channels ch0 .. ch0 + c of a tensor
     whose statistics `stats` [nb', groups, 2] were taken over groups of cpg channels (cs_groupnorm_apply_range); sample n
-    of x uses stats[n].  split16=True returns the Split16 operand pair."""
+    of x uses stats[n].  split16=True returns the Split16 operand pair; r5: wino=v the Winograd-W operand of the conv that
+    reads it (x: [nb, d, h, w, c])."""
     _chk(x, "x"); _chk(stats, "stats")
-    nb = x.shape[0]
-    m, c, ldx = rows_ld(x, "x")
-    groups = stats.shape[1]
-    if stats.shape[0] < nb or not stats.is_contiguous() or gamma.numel() != c or beta.numel() != c:
+    c = rows_ld(x, "x")[1]
+    if stats.shape[0] < x.shape[0] or not stats.is_contiguous() or gamma.numel() != c or beta.numel() != c:
         raise L.CsError("groupnorm_apply_range: stats / gamma / beta do not match x")
-    lib = L.load()
-    if wino and _sw("SPLIT16_PRODUCERS"):       # r5: the Winograd-W operand of the conv that reads it (x: [nb, d, h, w, c])
-        v = 4 if wino == 4 else 2
-        if x.dim() != 5 or int(x.shape[3]) % v or c % 8:
-            raise L.CsError("groupnorm_apply_range(wino=v) needs x as [nb, d, h, w, c] with w % v == 0 and c % 8 == 0")
-        d_, h_, w_ = int(x.shape[1]), int(x.shape[2]), int(x.shape[3])
-        yh = torch.empty((v + 2, nb, d_, h_, w_ // v, c), dtype=torch.float16, device=x.device)
-        yl = torch.empty_like(yh)
-        a_sc = float(a_scale or A_SCALE) * (0.5 if v == 2 else 0.0625)
-        L.check(lib.cs_groupnorm_apply_wino_range(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                  yh.data_ptr(), yl.data_ptr(), nb, d_, h_, w_, c, ldx, c, groups, cpg,
-                                                  ch0, act, a_sc, v, status_word(x.device).data_ptr(), _stream()),
-                "cs_groupnorm_apply_wino_range")
-        return Wino16(yh, yl, a_sc, (nb, d_, h_, w_), v)
-    if split16 and _sw("SPLIT16_PRODUCERS"):
-        yh = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-        yl = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-        a_sc = float(a_scale or A_SCALE)
-        L.check(lib.cs_groupnorm_apply_split16_range(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                     yh.data_ptr(), yl.data_ptr(), nb, m // nb, c, ldx, c, groups, cpg,
-                                                     ch0, act, a_sc, status_word(x.device).data_ptr(), _stream()),
-                "cs_groupnorm_apply_split16_range")
-        return Split16(yh, yl, a_sc)
-    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    L.check(lib.cs_groupnorm_apply_range(x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
-                                         nb, m // nb, c, ldx, c, groups, cpg, ch0, act, _stream()),
-            "cs_groupnorm_apply_range")
-    return y
+    form = _gn_form(x, c, split16, wino, "groupnorm_apply_range")
+    return _gn_emit(x, stats, gamma, beta, stats.shape[1], act, form, a_scale, rng=(cpg, ch0))
 
 
 def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5, out: Optional[Tensor] = None,

@@ -27,7 +27,7 @@ LIPSCHITZ = 1.13
 # 0.5 E is the headroom the gate was specified with, so the table uses a base at which the emulation shows it.
 SEED_BASE = 5000
 
-# Winograd B^T along W as written in gn_apply_wino16_kernel / gn_apply_wino43_kernel: image q = sum_j BT[q][j] d_j with
+# Winograd B^T along W as written in gn_wino_bt (gn_apply_wino_kernel<2, 4> / <4, 4>): image q = sum_j BT[q][j] d_j with
 # d_j = y[variant * tile - 1 + j], zero outside the line
 BT = {2: [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]],
       4: [[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
@@ -110,7 +110,7 @@ _add("split16", "2x37x1032-g4", "gn16", (2, 37, 1032), 4, ACT_SILU, S16, "ch4 = 
 _add("split16", "range-ch8-3x37x24-g2", "gn16", (3, 37, 24), 2, ACT_SILU, S16, "ch0 = 8 at cpg = 12: the range starts mid-group", s=64.0,
      ch0=8, nc=16)
 
-W2, W4 = "gn_apply_wino16_kernel", "gn_apply_wino43_kernel<4>"
+W2, W4 = "gn_apply_wino_kernel<2,4>", "gn_apply_wino_kernel<4,4>"
 for grp, var, kern, w0, w1 in (("wino23", 2, W2, 2, 6), ("wino43", 4, W4, 4, 12)):
     _add(grp, f"1x1x7x{w0}x8-g2", "wino", (1, 1, 7, w0, 8), 2, ACT_SILU, kern,
          f"w = {w0}: one tile per line, both pads in it; 7 lines under 128 line-lanes", s=128.0, variant=var)

@@ -3,7 +3,7 @@ pack_f16x3_wino_kernel, the stacked position GEMMs of conv_wino, wino_out_kernel
 (splitk_reduce_kernel, splitk_reduce_epi_kernel), piecewise.  No test functions here.
 
 The transforms, written out (F(R,3) along W, P = R + 2 positions, tile t of a line covers outputs R t .. R t + R - 1):
-  image q   = sum_j BT[q][j] d[R t - 1 + j]        (zero outside the line; gn_apply_wino*_kernel, tests/_norm_cases.py::BT)
+  image q   = sum_j BT[q][j] d[R t - 1 + j]        (zero outside the line; gn_apply_wino_kernel, tests/_norm_cases.py::BT)
   weight q  = sum_k G[q][k] g[.., k]               (pack_f16x3_wino_kernel)
   m_q       = the 3x3x1 conv (pads 1 / 1 / 0) of image q with weight q over (D, H, W / R)      (the position GEMMs)
   output e  = sum_q AT[e][q] m_q                   (wino_out_kernel)

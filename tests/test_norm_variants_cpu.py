@@ -93,17 +93,23 @@ def test_pair_split_terms():
 
 
 def test_table_names_every_launch_site_of_cs_norm():
-    """the CS_LAUNCH( sites of cs_norm.hip, recounted from the source, are exactly the kernels the table's cases name: a kernel
-    or instantiation added to (or dropped from) the file must get (lose) its case"""
+    """the CS_LAUNCH( sites of cs_norm.hip (10, and 2 CS_LN_LAUNCH( sites of three instantiations each), recounted from the
+    source, are exactly the kernels the table's cases name: a kernel or instantiation added to (or dropped from) the file must
+    get (lose) its case"""
     src = SRC.read_text()
     wv = re.search(r"#else\s*\n\s*constexpr int WV = (\d+);", src).group(1)
-    sites = re.findall(r"CS_LAUNCH\(\s*([A-Za-z_0-9]+(?:<[^>]*>)?)", src)
-    found = {s.replace("<WV>", f"<{wv}>") for s in sites}
+    sites = re.findall(r"CS_LAUNCH\(\s*\(?([A-Za-z_0-9]+(?:<[^>]*>)?)", src)
+    # a CS_LN_LAUNCH site launches the MAXV instantiations that cs_ln_pair.h's macro spells out
+    maxv = re.findall(r"CS_LAUNCH\(kernel<(\d+)>", (SRC.parent / "cs_ln_pair.h").read_text())
+    ln_sites = re.findall(r"CS_LN_LAUNCH\(\s*([A-Za-z_0-9]+)", src)
+    sites += [f"{k}<{v}>" for k in ln_sites for v in maxv]
+    found = {s.replace("WV>", f"{wv}>").replace(" ", "") for s in sites}
     named = {k for c in N.CASES for k in c.kernels}
+    assert maxv == ["2", "4", "8"] and len(ln_sites) == 2
     assert len(sites) == len(found) == 16, sorted(found)
     assert named == found, (sorted(named - found), sorted(found - named))
     kernels = set(re.findall(r"__global__\s+__launch_bounds__\([^)]*\)\s+void\s+(\w+)", src))
-    assert len(kernels) == 11 and kernels == {k.split("<")[0] for k in found}, sorted(kernels)
+    assert len(kernels) == 10 and kernels == {k.split("<")[0] for k in found}, sorted(kernels)
 
 
 def test_table_reaches_the_branches_it_claims():

@@ -1,6 +1,7 @@
-"""Every kernel of commonscenes_amd/csrc/cs_norm.hip and every template instantiation behind its extern "C" entries (11 kernels,
-16 launch sites: gn_finalize_parts_kernel<1|4>, ln_kernel<2|4|8>, ln_pair_kernel<2|4|8>, gn_apply_wino43_kernel<4>, recounted
-from the source by test_norm_variants_cpu.py), each at the smallest shape that reaches the geometry branch it is in the table
+"""Every kernel of commonscenes_amd/csrc/cs_norm.hip and every template instantiation behind its extern "C" entries (10 kernels,
+16 instantiations at 12 launch sites: gn_finalize_parts_kernel<1|4>, gn_apply_wino_kernel<2,4|4,4>,
+and ln_kernel<2|4|8>, ln_pair_kernel<2|4|8> behind one CS_LN_LAUNCH site each, recounted from the source by
+test_norm_variants_cpu.py), each at the smallest shape that reaches the geometry branch it is in the table
 for (tests/_norm_cases.py: the table, the fp64 references, the bounds).  The entries are called through ctypes so that ld*,
 col0, nb_src and ncls are explicit.
 
@@ -457,7 +458,7 @@ def test_split16(c):
     assert all(_untouched(buf, v) for buf, v in (H, Lo, H2, Lo2, (yb, y)))
 
 
-# ---- wino: gn_apply_wino16_kernel, gn_apply_wino43_kernel<4> ----------------------------------------------------------------
+# ---- wino: gn_apply_wino_kernel<2, 4>, gn_apply_wino_kernel<4, 4> ----------------------------------------------------------------
 def _wino(c, lib, x, g, b, st, s, status, entry="range"):
     nb, d, h, w, ctot = c.shape
     ch0, nc = N.chan_range(c)
