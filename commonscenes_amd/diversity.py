@@ -1,5 +1,5 @@
-"""The diversity table of scripts/eval_3dfront.py (--evaluate_diversity, :577-762) and the Chamfer half of
-scripts/consistency_check.py (:68-101) behind the reference's names.
+"""The diversity table of scripts/eval_3dfront.py (--evaluate_diversity, :577-762) and the two tables of
+scripts/consistency_check.py (Chamfer :68-101; CLIP :82-90 over clip.py's image features) behind the reference's names.
 
 Both tables are the same three device steps -- resample a ragged set of vertex clouds (`sample_points`,
 helpers/util.py:31-44), normalise them (`normalize`, eval_3dfront.py:783-796), take the Chamfer distance of a list of pairs --
@@ -390,13 +390,13 @@ def scene_diversity(model, scene: dict, num_samples: int = 3, ddim_steps: int = 
 # ----------------------------------------------------------------------------------------------------------------------
 # consistency
 # ----------------------------------------------------------------------------------------------------------------------
-def _group(dist: np.ndarray, categories) -> dict:
+def _group(dist: np.ndarray, categories, key: str = "chamfer") -> dict:
     table: Dict[str, List[float]] = {}
     for c, v in zip(categories, dist):
         table.setdefault(str(c), []).append(float(v))
-    out = {c: {"pairs": len(v), "chamfer": float(np.mean(np.array(v, np.float64)))} for c, v in table.items()}
+    out = {c: {"pairs": len(v), key: float(np.mean(np.array(v, np.float64)))} for c, v in table.items()}
     n = len(dist)
-    out["total"] = {"pairs": n, "chamfer": float(np.sum(np.asarray(dist, np.float64)) / n) if n else None}
+    out["total"] = {"pairs": n, key: float(np.sum(np.asarray(dist, np.float64)) / n) if n else None}
     return out
 
 
@@ -410,6 +410,20 @@ def consistency_table(clouds: Tensor, pairs, categories: Sequence[str]) -> dict:
         raise ValueError("'total' is the table's own row")
     dist = chamfer_pairs(clouds, pairs).cpu().numpy().astype(np.float64) if len(pairs) else np.zeros((0,), np.float64)
     return _group(dist, categories)
+
+
+def clip_consistency_table(features: Tensor, pairs, categories: Sequence[str]) -> dict:
+    """consistency_check.py:82-90, the `CLIP AVG` table: torch.norm(feature_a - feature_b) of every listed pair of the
+    image features [N, E] (clip.CLIP.encode_image of the rendered object views) in one launch (cs_feature_pair_l2), averaged
+    per category (categories[k] names pair k) and in total as sum / count, in float64."""
+    from .clip import feature_pair_l2
+    pairs = np.asarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, np.int64).reshape(-1, 2)
+    if len(categories) != len(pairs):
+        raise ValueError(f"{len(categories)} category names for {len(pairs)} pairs")
+    if "total" in [str(c) for c in categories]:
+        raise ValueError("'total' is the table's own row")
+    dist = feature_pair_l2(features, pairs).cpu().numpy().astype(np.float64) if len(pairs) else np.zeros((0,), np.float64)
+    return _group(dist, categories, key="clip")
 
 
 def consistency_from_meshes(verts_list, pairs, categories: Sequence[str], points: int = 5000, seed: int = 47) -> dict:

@@ -237,6 +237,13 @@ SIGNATURES = {
     "cs_view_raster": (_i, [_f, _f, _l, _f, _l, _f, _f, _f, _f, _i, _i, _fl, _f, _f, _s]),
     "cs_view_shade": (_i, [_f, _f, _f, _f, _f, _f, _l, _f, _l, _f, _f, _f, _f, _i, _i, C.POINTER(C.c_float), _f, _f, _f, _f,
                            _s]),
+    "cs_clip_patchify": (_i, [_f, _f, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _fl, _fl, _s]),
+    "cs_clip_assemble_image_tokens": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _s]),
+    "cs_clip_embed_text": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _s]),
+    "cs_clip_quick_gelu": (_i, [_f, _f, _l, _i, _i, _i, _s]),
+    "cs_clip_attn_causal": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _s]),
+    "cs_clip_pool_eot": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
+    "cs_feature_pair_l2": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _s]),
     "cs_abi_version": (_i, []),
 }
 

@@ -1144,6 +1144,48 @@ int cs_view_shade(const uint64_t* keys, const float* world, const float* normals
                   int n, int size, const float* eye3, float* image, int64_t* pix_to_face, float* zbuf, float* bary,
                   cs_stream_t stream);
 
+/*
+ * OpenAI CLIP ViT-B/32 (clip/model.py) -- the pieces the GEMM, LayerNorm and unmasked-attention entries do not cover
+ * (csrc/cs_clip.hip).  Additions to ABI 18; every entry only launches, none synchronises; all math is fp32.
+ *
+ * cs_clip_patchify: img uint8 [nb][s][s][3] (HWC) -> out fp32 [nb * g * g][ldo], g = s / p, the A operand of conv1 as a GEMM:
+ *   out[(b g + gy) g + gx][c p p + py p + px] = ((u / 255) - mean[c]) / std[c], u = img[b][gy p + py][gx p + px][c];
+ *   every operation rounded to fp32, both divisions the IEEE ones (torchvision's ToTensor + Normalize).  Columns are in
+ *   (c, py, px) order: conv1.weight.view(width, 3 p p) is the GEMM weight.  CS_EINVAL for s % p != 0 or ldo < 3 p p.
+ * cs_clip_assemble_image_tokens: x[b][0] = class_embedding + pos[0]; x[b][1 + t] = patch_out[b ntok + t] + pos[1 + t];
+ *   patch_out [nb * ntok][ldp], pos [ntok + 1][w] dense, x [nb * (ntok + 1)][ldx].
+ * cs_clip_embed_text: x[b t_len + t] = token_embedding[ids[b][t]] + pos[t]; token_embedding [vocab][w] and pos [t][w] dense,
+ *   ids int32 on the device.  An id is compared with `vocab` before anything is read through it: a bad one writes a NaN row
+ *   and sets bit 0 of the sticky device word *err (as cs_cloud_resample does); nothing is dereferenced.
+ * cs_clip_quick_gelu: y = x * sigmoid(1.702 x) over [m][c] rows (y may be x).  The product 1.702 x is carried in two floats,
+ *   so the result is within a few 1e-7 relative of the exact value down to the negative tail; large |x| give -0 / x, never a
+ *   NaN; a NaN input stays NaN.
+ * cs_clip_attn_causal: out[b][i][h dh + d] = sum_{j <= i} softmax_{j <= i}(scale q_i . k_j) v_j[d] -- the text tower's mask.
+ *   q, k, v, out: [nb][t][ld*] with head h at columns [h dh, (h + 1) dh), as cs_attn_selfattn (views of the fused in_proj
+ *   output).  One workgroup per (batch, head), K and V staged once in LDS.  A key j > i is never scored and never summed: row i
+ *   does not depend on its K / V values; a row's arithmetic depends on (i, dh) only.  t <= 128, dh <= 64, dh % 4 == 0,
+ *   ld* % 4 == 0, 16-byte aligned bases: anything else is CS_EINVAL.
+ * cs_clip_pool_eot: out[b] = x[b][j*], j* the position of the FIRST maximum of ids[b][0..t) (torch.argmax on a tokenised
+ *   text: the end-of-text token has the largest id).  x [nb * t][ldx], out [nb][ldo].
+ * cs_feature_pair_l2: out[k] = ||f[pairs[k][0]] - f[pairs[k][1]]||_2 for f [n][ld] (e columns), pairs int32 [npairs][2] on the
+ *   device, one wave per pair (consistency_check.py:65).  out[k] depends on the two rows only: (a, a) gives exactly 0, a
+ *   repeated pair the same bits.  An index outside [0, n) writes NaN and sets bit 0 of *err; nothing is read through it.
+ * CS_EINVAL for NULL pointers and sizes < 1.
+ */
+int cs_clip_patchify(const uint8_t* img, float* out, int nb, int s, int p, int ldo, float mean0, float mean1, float mean2,
+                     float std0, float std1, float std2, cs_stream_t stream);
+int cs_clip_assemble_image_tokens(const float* patch_out, const float* class_embedding, const float* pos, float* x, int nb,
+                                  int ntok, int w, int ldp, int ldx, cs_stream_t stream);
+int cs_clip_embed_text(const float* token_embedding, const int32_t* ids, const float* pos, float* x, int nb, int t, int w,
+                       int vocab, int ldx, int32_t* err, cs_stream_t stream);
+int cs_clip_quick_gelu(const float* x, float* y, int64_t m, int c, int ldx, int ldy, cs_stream_t stream);
+int cs_clip_attn_causal(const float* q, const float* k, const float* v, float* out, int nb, int t, int heads, int dh, int ldq,
+                        int ldk, int ldv, int ldo, float scale, cs_stream_t stream);
+int cs_clip_pool_eot(const float* x, const int32_t* ids, float* out, int nb, int t, int w, int ldx, int ldo,
+                     cs_stream_t stream);
+int cs_feature_pair_l2(const float* f, const int32_t* pairs, float* out, int n, int e, int npairs, int ld, int32_t* err,
+                       cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

@@ -10,13 +10,22 @@
         prints its numbers and both wall times (second call each), plus the two device launches' own times.
 
     python tools/diversity_table.py --consistency FILE.json --meshes DIR [--mapping FILE.json] [--points 5000] [--seed 47]
-        the Chamfer half of scripts/consistency_check.py (:68-101; its CLIP half needs CLIP).  FILE.json is what
+                                    [--images DIR --clip {MODEL.pt | synthetic} [--time-batch N]]
+        scripts/consistency_check.py: its Chamfer half (:68-101) and, with --images, its CLIP half (:58-66, :82-90).  FILE.json is what
         scripts/collect_consistency.py:284-300 writes: {"scans": [{"scan": name, "objects": {id: class name},
         "consistency": [[id, id, ...], ...]}]}; --mapping maps the fine class names to the coarse ones, as the script does
         for the small vocabulary.  Meshes are DIR/<scan>/<name>_<classid>_<id>.obj; the class id is whatever the exporter
         wrote (the file is found by name and instance id).  Vertices are read from the `v` lines as they stand:
         trimesh.load, which the script uses, also merges duplicate vertices, this reader does not.  Prints one
         `CONSISTENCY_TABLE {...}` JSON line.
+        --images DIR adds a `clip` block to that line: the rendered views DIR/<scan>/<name>_<classid>_<id>.png
+        (object_views.py writes them; found by name and instance id like the meshes) go through CLIP's preprocess and
+        commonscenes_amd.clip.CLIP.encode_image, and every pair's ||f_a - f_b|| is averaged per category and in total
+        (diversity.clip_consistency_table).  --clip MODEL.pt is OpenAI's ViT-B-32.pt (torch.jit.load, else torch.load);
+        --clip synthetic takes ViT-B/32 shapes with clip.synth_clip_state_dict weights, vision tower only (the figures then
+        mean nothing; the route is the same).  The reference runs CLIP in fp16, this is an fp32 forward: tables agree to the
+        low digits, not per bit.  --time-batch N also reports (never gates on) the time of one encode_image call on N
+        random images, second call, device events.  Without --images the output is what it was.
 """
 import argparse
 import json
@@ -161,6 +170,44 @@ def run_synthetic(a):
     print("DIVERSITY_TABLE " + json.dumps(res), flush=True)
 
 
+_CLIP_MODELS = {}
+
+
+def clip_model(spec):
+    """--clip: 'synthetic' (ViT-B/32 shapes, synthetic weights, vision tower only) or a checkpoint path; built once"""
+    from commonscenes_amd import clip as K
+    if spec not in _CLIP_MODELS:
+        if spec == "synthetic":
+            sd = K.synth_clip_state_dict({"vision": K.VIT_B_32["vision"]}, 0)
+            _CLIP_MODELS[spec] = K.CLIP("cuda").load_state_dict(sd)
+        else:
+            _CLIP_MODELS[spec] = K.load_checkpoint(spec, "cuda")
+    return _CLIP_MODELS[spec]
+
+
+def clip_block(a, image_files, pairs, cats):
+    from commonscenes_amd import clip as K
+    from commonscenes_amd.diversity import clip_consistency_table
+    model = clip_model(a.clip)
+    if model.vision is None:
+        raise SystemExit(f"--clip {a.clip}: no vision tower in the checkpoint")
+    size = model.vision.resolution
+    feats = [model.encode_image(K.preprocess(image_files[i:i + 64], size)) for i in range(0, len(image_files), 64)]
+    feats = torch.cat(feats) if feats else torch.zeros((1, 1), device="cuda")          # (no pairs: only the empty total row)
+    block = dict(model=a.clip, images=len(image_files), resolution=size, table=clip_consistency_table(feats, pairs, cats))
+    if a.time_batch:
+        batch = torch.from_numpy(np.random.default_rng(0).integers(0, 256, size=(a.time_batch, size, size, 3), dtype=np.uint8))
+        batch = batch.cuda()
+        for _ in range(2):                                       # the second call is the figure
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            model.encode_image(batch)
+            e1.record()
+            torch.cuda.synchronize()
+            block["encode_image_ms"], block["time_batch"] = e0.elapsed_time(e1), a.time_batch
+    return block
+
+
 def run_consistency(a):
     from commonscenes_amd.diversity import consistency_from_meshes, read_obj_vertices
     with open(a.consistency) as fh:
@@ -170,7 +217,7 @@ def run_consistency(a):
         with open(a.mapping) as fh:
             mapping = json.load(fh)
     name_of = lambda n: mapping[n] if mapping is not None else n
-    verts, where, pairs, cats = [], {}, [], []
+    verts, where, pairs, cats, image_files = [], {}, [], [], []
 
     def cloud(scan, name, oid):
         key = (scan, str(oid))
@@ -178,6 +225,11 @@ def run_consistency(a):
             found = sorted((Path(a.meshes) / scan).glob(f"{name}_*_{oid}.obj"))
             if len(found) != 1:
                 raise SystemExit(f"{scan}: expected one mesh {name}_<classid>_{oid}.obj, found {len(found)}")
+            if a.images:                                         # consistency_check.py:58-59: the same stem, .png
+                img = sorted((Path(a.images) / scan).glob(f"{name}_*_{oid}.png"))
+                if len(img) != 1:
+                    raise SystemExit(f"{scan}: expected one image {name}_<classid>_{oid}.png, found {len(img)}")
+                image_files.append(img[0])
             where[key] = len(verts)
             verts.append(read_obj_vertices(found[0]))
         return where[key]
@@ -191,7 +243,10 @@ def run_consistency(a):
             pairs.append((cloud(scan["scan"], sub, sub_id), cloud(scan["scan"], obj, obj_id)))
             cats.append(sub)
     table = consistency_from_meshes(verts, pairs, cats, points=a.points, seed=a.seed)
-    print("CONSISTENCY_TABLE " + json.dumps(dict(meshes=len(verts), points=a.points, seed=a.seed, table=table)), flush=True)
+    res = dict(meshes=len(verts), points=a.points, seed=a.seed, table=table)
+    if a.images:
+        res["clip"] = clip_block(a, image_files, pairs, cats)
+    print("CONSISTENCY_TABLE " + json.dumps(res), flush=True)
 
 
 def main():
@@ -210,11 +265,18 @@ def main():
                     "trimesh.load merges duplicate vertices, this reader does not")
     ap.add_argument("--mapping", metavar="FILE.json", default=None, help="fine -> coarse class names (mapping_no_stool.json)")
     ap.add_argument("--seed", type=int, default=47)
+    ap.add_argument("--images", metavar="DIR", default=None, help="DIR/<scan>/<name>_<classid>_<id>.png: adds the CLIP half "
+                    "(consistency_check.py:58-66, :82-90) as a `clip` block; needs --clip")
+    ap.add_argument("--clip", metavar="MODEL.pt|synthetic", default=None, help="OpenAI's ViT-B-32.pt, or `synthetic`: ViT-B/32 "
+                    "shapes with synthetic weights (vision tower only)")
+    ap.add_argument("--time-batch", type=int, default=0, help="also report the time of encode_image on N random images")
     a = ap.parse_args()
     if a.synthetic == bool(a.consistency):
         ap.error("give --synthetic or --consistency FILE.json")
     if a.consistency and not a.meshes:
         ap.error("--consistency needs --meshes DIR")
+    if bool(a.images) != bool(a.clip) or (a.images and not a.consistency):
+        ap.error("--images DIR and --clip MODEL go together, with --consistency")
     if a.synthetic and a.samples < 2:
         ap.error("diversity needs at least two runs per object")
     run_synthetic(a) if a.synthetic else run_consistency(a)
