@@ -26,7 +26,8 @@ first asserts through cs_conv_wino_ok / cs_conv_wino_plan_info that the library 
    partial tiles the call left in the test's own workspace: bound, bit equality, gn_part, pair output as in 3.
 7. Refusals: CS_EINVAL with the output untouched, host only.
 
-Not covered here: the fused in-kernel reduce (test_fused_splitk_gpu.py), up2_reduce_scatter_kernel (test_f16x3_gpu.py), the K-wave
+Not covered here: the fused in-kernel reduce (test_fused_splitk_gpu.py), up2_reduce_scatter_kernel (test_up2_variants_gpu.py: slice
+counts 2 / 9 / 10 / 17, read back from the workspace footprint), the K-wave
 kernel (test_kwave_gpu.py), the GroupNorm producer of the operand images (test_norm_variants_gpu.py), the workload's own shapes
 (test_wino_gpu.py).  Measured values: profiles/wino_variants_parity.txt (nothing here reads them)."""
 import ctypes as C
