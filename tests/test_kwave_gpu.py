@@ -5,7 +5,12 @@ at one or two objects).
 Same operand values and scales as every F16X3 tile, the K sum partitioned into four contiguous ranges: against fp64 at
 the per-op gate, against the one-chain 64x64 tile within fp32 summation order; the single epilogue's extras -- GroupNorm
 partial sums (64-row statistics tiles) and the interleaved operand pair -- against a pass over the tensor / the fp32
-hand-over (bit for bit: same values converted the same way); auto-selection only where every tile is resident at once."""
+hand-over (bit for bit: same values converted the same way); auto-selection only where every tile is resident at once.
+
+These are the workload's shapes, contiguous, gated on the whole tensor.  The kernel's edges -- waves with an empty K range, the
+ring's wrap and tails, partial K chunks, one-row / one-float4 edge tiles, small and ragged grids, operands as views between NaN
+bands, worst row / column, the a_bound rule at its clamps, the launch's refusals -- are test_kwave_variants_gpu.py's
+(table: tests/_kwave_cases.py)."""
 import ctypes as C
 
 import pytest
