@@ -43,6 +43,7 @@ __device__ __forceinline__ f32x4 cs_geglu4(f32x4 x, const f32x4& g) {
 }
 
 // ---- 2. the interleaved operand pair (CsConvGemm.out_format = 2) of v * out_scale ----
+// Two forms, one conversion: cs_pair16 (partner lane = lane ^ 1) and cs_pair16_half32 (partner lane = lane ^ 32).
 // A row is 64-byte chunks of 16 columns = [hi 0-7 | lo 0-7 | hi 8-15 | lo 8-15] (fp16 halves; hi = half(o), lo = half(o - hi)).
 // PRECONDITION: adjacent lanes 2t / 2t + 1 hold columns 8g .. 8g+3 / 8g+4 .. 8g+7 of ONE row (`odd` = the second of them),
 // and the call sits in a branch that is uniform over the wave: every lane takes part in the half swap (quad_perm 1,0,3,2),
@@ -69,6 +70,34 @@ __device__ __forceinline__ cs_u32x4 cs_pair16(const f32x4& v, float out_scale, b
   r[1] = odd ? recv[1] : H[1];
   r[2] = odd ? L[0] : recv[0];
   r[3] = odd ? L[1] : recv[1];
+  return r;
+}
+// The second form, for a TRANSPOSED 32x32 MFMA accumulator (cs_gemm_f16x3.hip, TR kernels): the two halves of a row's eight
+// columns sit 32 lanes apart, not one.  PRECONDITION: lanes l / l + 32 (l < 32) hold columns 8g .. 8g+3 / 8g+4 .. 8g+7 of ONE
+// row, the whole wave is active (v_permlane32_swap ignores EXEC for what it reads; a masked lane passes v = 0).  The swap
+// exchanges the upper half of the hi words with the lower half of the lo words, so lane l ends with [hi 8g .. 8g+7] and lane
+// l + 32 with [lo 8g .. 8g+7]: one 16-byte store each at byte cs_pair_off(first column of the lane) of the row, as above.
+// The conversion is cs_pair16's, expression for expression.
+__device__ __forceinline__ cs_u32x4 cs_pair16_half32(const f32x4& v, float out_scale, float& oamax) {
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  h4 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float o = v[e] * out_scale;
+    oamax = fmaxf(oamax, fabsf(o));
+    hi[e] = (_Float16)o;
+    lo[e] = (_Float16)(o - (float)hi[e]);
+  }
+  const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
+  // (vdst = H, src = L: lanes 32-63 of H <-> lanes 0-31 of L)
+  const auto s0 = __builtin_amdgcn_permlane32_swap(H[0], L[0], false, false);
+  const auto s1 = __builtin_amdgcn_permlane32_swap(H[1], L[1], false, false);
+  cs_u32x4 r;
+  r[0] = s0[0];      // lower lane: own hi 0-3      upper lane: the lower lane's lo 0-3
+  r[1] = s1[0];
+  r[2] = s0[1];      // lower lane: the upper lane's hi 4-7      upper lane: own lo 4-7
+  r[3] = s1[1];
   return r;
 }
 __device__ __forceinline__ int cs_pair_off(int col) { return (col >> 4) * 64 + ((col & 8) ? 32 : 0) + ((col & 4) ? 16 : 0); }

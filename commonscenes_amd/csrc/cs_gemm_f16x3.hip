@@ -21,7 +21,19 @@
 //     wait vmcnt(B_PW) [A(k+1) and older landed] ; s_barrier ; MFMAs on chunk k || issue DMA(k+2), split A(k+1)
 // K order: channel chunk OUTER, tap INNER (the 27 taps of one 16-channel chunk re-touch only this tile's rows
 // + halo, so they hit L1/L2 instead of re-streaming the activation tensor per tap).
-// fp16 32x32x16 operand map: lane l holds row/col l&31 and k = 8*(l>>5) .. 8*(l>>5)+7; C/D as for fp32.
+// fp16 32x32x16 operand map: lane l holds row/col l&31 and k = 8*(l>>5) .. 8*(l>>5)+7; C/D as for fp32: lane l holds
+// column l&31 and rows (r&3) + 8*(r>>2) + 4*(l>>5) of the block in register r.
+// TR (the pointwise instantiations): both operands have that one fragment shape, so the K loop passes them SWAPPED --
+// mfma(b_frag, a_frag) -- and the block comes out transposed at no cost: lane l holds output ROW l&31, and registers
+// 4g .. 4g+3 are the four consecutive columns 8g + 4*(l>>5) + 0..3 of block j, a float4 of the row.  The same exact
+// products are summed over the same k: the bits do not change.
+// Epilogues.  Untransposed kernels stage the accumulators through the idle ring (a lane owns a column, stores want rows): the
+// pipelined path (bias / row-vector rows and the next pass's residual rows LDS-DMA'd), the plain float4 path, the scalar one.
+// TR kernels store straight from registers where the pipelined path would serve and no GroupNorm partials are asked for: the
+// residual float4s are loaded at the store addresses in one or two batches, bias and row vector come from an LDS area the
+// prologue fills beyond the ring, GEGLU pairs column c with c + WCOLS/2 of the same lane, the pair output exchanges halves
+// across lanes l / l+32 (cs_epilogue.h::cs_pair16_half32); no staging, no barrier.  Everything else on a TR kernel first
+// puts the blocks back into the untransposed layout through LDS and then runs the code of the other kernels unchanged.
 #include <cstdlib>
 #include <cstring>
 #include "cs_f16x3.h"
@@ -243,6 +255,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
   constexpr int BN = 32 * WNB * WAVES_N;
   constexpr int NW = WAVES_M * WAVES_N;            // waves per workgroup (4, or 8 for the 256-row tile)
   constexpr int NT = 64 * NW;
+  // TR: the pointwise kernels accumulate the TRANSPOSED product (operand map in the file header): a lane then owns float4s of
+  // one output row, and the epilogue stores from registers.  Derived, not a template argument: the launch table is unchanged.
+  constexpr bool TR = PW;
   // ---- LDS map (bytes) ----
   static_assert(!SLAB || (WMB <= 2 && WAVES_N == 1), "slab path: one or two row blocks per wave");
   static_assert(!PAIR || (!PRE && SLAB == 0), "interleaved operand pairs: per-tap gather path only");
@@ -568,6 +583,28 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
     }
   };
 
+  // TR: the tile's bias row and the row-vector row of its FIRST sample go to the (pointwise: unused) row-table area beyond the
+  // ring BEFORE the first chunk's DMAs -- the oldest transfers in flight, so the prologue's counted wait and barrier cover
+  // them and no vmcnt of the K loop changes; the register-direct epilogue reads them without waiting for the ring to drain.
+  constexpr int TRV = ROWBASE;                     // float [256] bias row, float [256] row-vector row
+  if constexpr (TR) {
+    static_assert(TRV + 2048 <= LDS_BYTES && BN <= 256 && (BN + 63) / 64 <= NW, "bias / row-vector rows beyond the ring");
+    if (wave < (BN + 63) / 64) {                   // 4 bytes per lane; columns past cout read zero
+      const unsigned col = (unsigned)(64 * wave + lane);
+      const unsigned off = col < (unsigned)BN ? (unsigned)(n0 + (int)col) * 4u : OOB;
+      float* const tv = reinterpret_cast<float*>(smem + TRV);
+      if (p.bias) {
+        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, (unsigned)p.cout * 4u, 0x00020000);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, tv + 64 * wave, 4, off, 0, 0, 0);
+      }
+      if (p.rowvec) {
+        const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(p.rowvec + (int64_t)(m0 / p.rv_rows) * p.ldrv), 0, (unsigned)p.cout * 4u, 0x00020000);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, tv + 256 + 64 * wave, 4, off, 0, 0, 0);
+      }
+    }
+  }
+
   f32x16 acc[WMB][WNB];
 #pragma unroll
   for (int i = 0; i < WMB; ++i)
@@ -780,9 +817,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
       const h8 bl = *reinterpret_cast<const h8*>(s + b_frag + B_BYTES + j * 512);
 #pragma unroll
       for (int i = 0; i < WMB; ++i) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+        if constexpr (TR) {            // the two operands have one fragment shape: swapped, the block comes out transposed
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al[i], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah[i], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah[i], acc[i][j], 0, 0, 0);
+        } else {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+        }
       }
       if (j == 0) {                    // behind the first MFMAs: launch the prefetch, then split A(k+1)
         if (!(CS_ABLATE & 1)) issue_dma(dtap, dcc, dstage);
@@ -993,6 +1036,148 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
     const bool gstat = p.gn_part != nullptr;                 // per-(tile, column) GroupNorm partial sums
     const bool opair = p.out_format == 2;                    // `out` as the interleaved operand pair of out * out_scale
     if ((gstat || opair) && !piped && tid == 0 && p.status) atomicOr(p.status, CS_STATUS_INTERNAL);
+    if constexpr (TR) {
+      // ---- register-direct epilogue (TR kernels; what the pipelined path below serves, minus GroupNorm partials) ----
+      // acc[i][j][4 g + e] is output row wm0 + 32 i + l31, column wn0 + 8 t + 4 half + e of the wave, t = 4 j + g: a float4
+      // of the row.  No LDS staging, no barrier: the residual float4s of a batch of column groups are loaded at the store
+      // addresses, all at once, the bias / row-vector float4s come from the area the prologue filled, and every element
+      // takes the operations of cs_epi_terms4 in its order -- the bits of the staged paths.
+      if (piped && !gstat) {
+        typedef cs_u32x4 u32x4;
+        constexpr int NG = 4 * WNB;                            // column groups (of 8 columns) of the wave
+        constexpr int GB = (WMB * NG <= 16) ? NG : NG / 2;     // groups per residual batch: at most 16 float4s in flight
+        static_assert(NG % GB == 0 && WMB * GB <= 16, "residual batches");
+        const long long o_skip = (long long)m0 * p.ldo * 4, r_skip = (long long)m0 * p.ldr * 4;
+        const long long o_cols = geglu ? p.cout / 2 : p.cout;
+        const long long o_left = ((long long)(M - 1) * p.ldo + o_cols) * 4 - o_skip;
+        const long long r_left = has_res ? ((long long)(M - 1) * p.ldr + p.cout) * 4 - r_skip : 0;
+        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)((char*)p.out + o_skip), 0, o_left > 0x7FF00000LL ? 0x7FF00000u : (unsigned)o_left, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(has_res ? (const char*)p.res + r_skip : (const char*)p.out), 0,
+            r_left > 0x7FF00000LL ? 0x7FF00000u : (r_left > 0 ? (unsigned)r_left : 0u), 0x00020000);
+        const float* const tvb = reinterpret_cast<const float*>(smem + TRV) + wn0 + 4 * half;
+        const float* const tvr = tvb + 256;
+        const int cl = n0 + wn0 + 4 * half;                    // the lane's column of group 0
+        bool rok[WMB];
+        unsigned orow[WMB], rrow[WMB];
+#pragma unroll
+        for (int i = 0; i < WMB; ++i) {
+          const int row = wm0 + 32 * i + l31;
+          rok[i] = m0 + row < M;
+          orow[i] = (unsigned)(row * p.ldo) * 4u;
+          rrow[i] = (unsigned)(row * p.ldr) * 4u;
+        }
+        float oamax = 0.f;
+        if (geglu) {
+          // columns of the wave = [x (WCOLS/2) | gate (WCOLS/2)]: the partner of group t is group t + NG/2 of the same lane
+          constexpr int HG = NG / 2;
+          const int co = (n0 + wn0) / 2 + 4 * half;            // output column of the lane's group 0
+#pragma unroll
+          for (int t = 0; t < HG; ++t) {
+            f32x4 bx = {0.f, 0.f, 0.f, 0.f}, bg = bx;
+            if (p.bias) {
+              bx = *reinterpret_cast<const f32x4*>(tvb + 8 * t);
+              bg = *reinterpret_cast<const f32x4*>(tvb + 8 * (t + HG));
+            }
+#pragma unroll
+            for (int i = 0; i < WMB; ++i) {
+              f32x4 xv, gv;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                xv[e] = acc[i][t / 4][4 * (t % 4) + e] * acc_scale_;
+                gv[e] = acc[i][(t + HG) / 4][4 * ((t + HG) % 4) + e] * acc_scale_;
+              }
+              if (p.bias) {
+                xv += bx;
+                gv += bg;
+              }
+              xv = (CS_ABLATE & 32768) ? xv * gv : cs_geglu4(xv, gv);
+              const bool ok = rok[i];                          // (whole [x | gate] groups: no column past cout)
+              if (opair) {
+                if (!ok) xv = f32x4{0.f, 0.f, 0.f, 0.f};
+                const u32x4 pk = cs_pair16_half32(xv, p.out_scale, oamax);
+                unsigned off = ok ? orow[i] + (unsigned)cs_pair_off(co + 8 * t) : OOB;
+                if (CS_ABLATE & 16384) off = OOB;
+                __builtin_amdgcn_raw_buffer_store_b128(pk, ors, off, 0, 0);
+              } else {
+                unsigned off = ok ? orow[i] + (unsigned)(co + 8 * t) * 4u : OOB;
+                if (CS_ABLATE & 16384) off = OOB;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, xv), ors, off, 0, 0);
+              }
+            }
+          }
+        } else {
+#pragma unroll
+          for (int t0 = 0; t0 < NG; t0 += GB) {
+            f32x4 rv[WMB][GB];
+            if (has_res) {
+#pragma unroll
+              for (int i = 0; i < WMB; ++i)
+#pragma unroll
+                for (int tt = 0; tt < GB; ++tt) {
+                  const int n = cl + 8 * (t0 + tt);
+                  const unsigned off = (rok[i] && n < p.cout) ? rrow[i] + (unsigned)n * 4u : OOB;
+                  rv[i][tt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrs, off, 0, 0));
+                }
+            }
+#pragma unroll
+            for (int tt = 0; tt < GB; ++tt) {
+              const int t = t0 + tt;
+              const int n = cl + 8 * t;
+              f32x4 bv = {0.f, 0.f, 0.f, 0.f}, vv = bv;
+              if (p.bias) bv = *reinterpret_cast<const f32x4*>(tvb + 8 * t);
+              if (p.rowvec) vv = *reinterpret_cast<const f32x4*>(tvr + 8 * t);
+#pragma unroll
+              for (int i = 0; i < WMB; ++i) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[i][t / 4][4 * (t % 4) + e] * acc_scale_;
+                if (p.bias) v += bv;
+                if (p.rowvec) v += vv;
+                if (p.act != CS_ACT_NONE) {
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) v[e] = cs_act(v[e], p.act);
+                }
+                if (has_res) v += rv[i][tt];
+                const bool ok = rok[i] && n < p.cout;
+                if (opair) {
+                  if (!ok) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                  const u32x4 pk = cs_pair16_half32(v, p.out_scale, oamax);
+                  unsigned off = ok ? orow[i] + (unsigned)cs_pair_off(n) : OOB;
+                  if (CS_ABLATE & 16384) off = OOB;
+                  __builtin_amdgcn_raw_buffer_store_b128(pk, ors, off, 0, 0);
+                } else {
+                  unsigned off = ok ? orow[i] + (unsigned)n * 4u : OOB;
+                  if (CS_ABLATE & 16384) off = OOB;
+                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, off, 0, 0);
+                }
+              }
+            }
+          }
+        }
+        cs_pair_flag(p, opair, oamax);
+        return;
+      }
+      // Every other epilogue of a TR kernel (GroupNorm partials, scale / shift, the scalar form, a tile across two row-vector
+      // samples, K slices): cold.  Each wave puts its 32x32 blocks back into the untransposed register layout through the
+      // ring's LDS -- written by (row, column), read back by (column, row), 33-float rows -- and the code below runs as it
+      // does on the other kernels, on the same values.
+      {
+        static_assert(NW * 32 * 33 * 4 <= DUMP, "untranspose scratch must fit in the ring");
+        __syncthreads();                                       // every wave has left the ring
+        float* const tb = reinterpret_cast<float*>(smem) + wave * (32 * 33);
+#pragma unroll
+        for (int i = 0; i < WMB; ++i)
+#pragma unroll
+          for (int j = 0; j < WNB; ++j) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tb[l31 * 33 + 8 * (r >> 2) + 4 * half + (r & 3)] = acc[i][j][r];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = tb[(8 * (r >> 2) + 4 * half + (r & 3)) * 33 + l31];
+          }
+      }
+    }
     if (piped) {
       __syncthreads();                                       // every wave has left the ring
       float* const ep = reinterpret_cast<float*>(smem + wave * EPB);
