@@ -10,7 +10,9 @@
 // query i need one shuffle with lane^32 and nothing else.
 //
 // Workgroup = 4 waves x 32 queries; K/V tiles of KT keys staged in LDS and shared by the 4 waves.
-#include "cs_common.h"
+// The online softmax, the store tail, the block map and the argument check are cs_attention_core.h's (shared with the
+// fp16-MFMA kernels of cs_attention_f16x3.hip); the fp32 LDS tile and the two fp32 MFMA loops are this kernel's own.
+#include "cs_attention_core.h"
 
 namespace {
 
@@ -35,11 +37,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ q,
   const int l31 = lane & 31;
   const int half = lane >> 5;
 
-  int bid = blockIdx.x;
-  const int qt = bid % qtiles;
-  bid /= qtiles;
-  const int h = bid % heads;
-  const int b = bid / heads;
+  int qt, b, h;
+  attn_block_map<false>(qtiles, heads, 0, qt, b, h);      // plain launch order: no padding, never refuses
 
   const int q0 = qt * 128 + wave * 32;
   const int qi = min(q0 + l31, nq - 1);
@@ -101,34 +100,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ q,
         sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[2 * t], qreg[t], sacc[jb], 0, 0, 0);
     }
 
-    // ---- online softmax (per query i = lane&31) ----
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = kt0 + jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (j >= nk) sacc[jb][r] = -INFINITY;
-        mloc = fmaxf(mloc, sacc[jb][r]);
-      }
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    const float mnew = fmaxf(mrun, mloc);
-    const float alpha = (mrun == -INFINITY) ? 0.f : expf(mrun - mnew);
-    float psum = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = expf(sacc[jb][r] - mnew);
-        sacc[jb][r] = pv;
-        psum += pv;
-      }
-    lrun = lrun * alpha + psum;
-    mrun = mnew;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
+    attn_softmax_tile<KT>(sacc, oacc, mrun, lrun, kt0, nk, half, AttnExpF());
 
     // ---- O^T += V^T P^T ----
 #pragma unroll
@@ -143,25 +115,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ q,
       }
   }
 
-  const float ltot = lrun + __shfl_xor(lrun, 32, 64);
-  const float inv = 1.0f / ltot;
-  if (q0 + l31 < nq) {
-    float* op = out + ((int64_t)b * nq + q0 + l31) * ldo + h * dh;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = 32 * d + 8 * g + 4 * half;
-        if (dd < dh) {
-          float4 o;
-          o.x = oacc[d][4 * g + 0] * inv;
-          o.y = oacc[d][4 * g + 1] * inv;
-          o.z = oacc[d][4 * g + 2] * inv;
-          o.w = oacc[d][4 * g + 3] * inv;
-          *reinterpret_cast<float4*>(op + dd) = o;
-        }
-      }
-  }
+  attn_store_out<DB>(oacc, lrun, 1.0f, out, b, nq, q0 + l31, ldo, h, dh, half);      // (ltot * 1.0f is exact)
 }
 
 template <int DB, int KT>
@@ -171,7 +125,7 @@ int launch_attn(const float* q, const float* k, const float* v, float* out, int 
   constexpr int DP = 32 * DB;
   const size_t smem = (size_t)KT * ((DP + 1) + (DP + 4)) * sizeof(float);
   const int qtiles = (nq + 127) / 128;
-  const int64_t grid = (int64_t)qtiles * heads * nb;
+  const int64_t grid = attn_grid<false>(qtiles, nb, heads);
   if (grid > 0x7fffffffLL) return CS_EINVAL;
   auto kern = attn_kernel<DB, KT>;
   if (smem > 64 * 1024) {
@@ -190,13 +144,7 @@ int launch_attn(const float* q, const float* k, const float* v, float* out, int 
 extern "C" int cs_attn_selfattn(const float* q, const float* k, const float* v, float* out, int nb,
                                 int nq, int nk, int heads, int dh, int ldq, int ldk, int ldv,
                                 int ldo, float scale, cs_stream_t stream) {
-  if (!q || !k || !v || !out || nb <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || dh <= 0)
-    return CS_EINVAL;
-  if ((dh & 3) || (ldq & 3) || (ldk & 3) || (ldv & 3) || (ldo & 3)) return CS_EINVAL;
-  if (ldq < heads * dh || ldk < heads * dh || ldv < heads * dh || ldo < heads * dh)
-    return CS_EINVAL;
-  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
-    return CS_EINVAL;
+  if (!attn_args_ok(q, k, v, out, nullptr, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo)) return CS_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (dh <= 32) return launch_attn<1, 64>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, s);
   if (dh <= 64) return launch_attn<2, 64>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, s);

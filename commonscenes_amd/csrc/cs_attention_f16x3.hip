@@ -6,11 +6,10 @@
 //                                          S^T accumulator registers (split into hi/lo in place)
 // each contraction = 3 v_mfma_f32_32x32x16_f16 (lo*hi + hi*lo + hi*hi), fp32 accumulate.
 //
-// Register -> key map of the 32x32 C/D layout: lane (i = lane&31, h = lane>>5) holds S^T[j][i] for
-// j = (r&3) + 8*(r>>2) + 4*h.  PV MFMA (jb, q) takes registers r = 8q..8q+7 as its 8 k-slots, so k-slot (h, e) is
-// key 32*jb + ((8q+e)&3) + 8*((8q+e)>>2) + 4*h; the V^T image stores key j at column pos(j) = j with bits 2 and 3
-// swapped, which makes those 8 keys one contiguous 16-byte read.
-#include "cs_common.h"
+// The register -> key map, the tile layout and every per-tile piece the kernels here share with each other and with the fp32
+// kernel are in cs_attention_core.h; this file keeps what is each kernel's own: how the K / V images reach LDS and the
+// schedule around the shared pieces.
+#include "cs_attention_core.h"
 #include "cs_f16x3.h"
 #include <cstdlib>
 
@@ -22,26 +21,12 @@ namespace {
 #endif
 constexpr int RING = CS_ATTN_RING > 0 ? CS_ATTN_RING : 1;
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+using h8 = attn_h8;
 
 constexpr float QK_SCALE = 16.0f;     // operand pre-scale (power of two) for Q*scale, K and V
 constexpr float P_SCALE = 1024.0f;    // probabilities are <= 1
-
-__device__ __forceinline__ void split1(float v, _Float16& hi, _Float16& lo) {
-  hi = (_Float16)v;
-  lo = (_Float16)(v - (float)hi);
-}
-
-// operand split that also tracks the lane's largest |operand| (overflow report, see CS_STATUS_F16X3_OVERFLOW)
-__device__ __forceinline__ void split1m(float v, _Float16& hi, _Float16& lo, float& amax) {
-  amax = fmaxf(amax, fabsf(v));
-  split1(v, hi, lo);
-}
-
-__device__ __forceinline__ int vpos(int j) {   // swap bits 2 and 3
-  return (j & ~12) | ((j & 4) << 1) | ((j & 8) >> 1);
-}
+constexpr float LOG2_P_SCALE = 10.0f;
+static_assert(P_SCALE == 1024.0f, "LOG2_P_SCALE = log2(P_SCALE)");
 
 // X1 = plain fp16 operands (hi halves only: one MFMA per product instead of three) -- the reduced-precision
 // "fp16 MFMA attention" option of BASELINE configs[4]; not the default, outside the fp32 parity gates.
@@ -54,17 +39,14 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
   // qs / ks / vs (r5): the power-of-two operand pre-scales of Q * scale, K and V -- 16 each by default (QK_SCALE), or the
   // static bounds' scales of cs_attn_selfattn_f16x3_scaled (a transformer block's q / k / v are Linear(LayerNorm(x)):
   // bounded by the weights alone)
-  constexpr int DP = 32 * DB;
+  using T = AttnTile<DB, KT>;
+  constexpr int DP = T::DP, LDK = T::LDK, LDV = T::LDV, JB = T::JB, KS = T::KS;
   float amax = 0.f;                    // largest |scaled Q / K / V operand| this lane converted to fp16
-  constexpr int LDK = DP + 8;          // halves; 16 consecutive rows hit 16 distinct 16-byte slots
-  constexpr int LDV = KT + 8;
-  constexpr int JB = KT / 32;
-  constexpr int KS = DP / 16;          // k-steps of the QK^T contraction
   extern __shared__ __attribute__((aligned(16))) _Float16 sm[];
   _Float16* Kh = sm;                   // [KT][LDK]
-  _Float16* Kl = Kh + KT * LDK;
-  _Float16* Vh = Kl + KT * LDK;        // [DP][LDV]  (V^T, permuted key order)
-  _Float16* Vl = Vh + DP * LDV;
+  _Float16* Kl = Kh + T::K_HALVES;
+  _Float16* Vh = Kl + T::K_HALVES;     // [DP][LDV]  (V^T, permuted key order)
+  _Float16* Vl = Vh + T::V_HALVES;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -72,20 +54,8 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
   const int l31 = lane & 31;
   const int half = lane >> 5;
 
-  // XCD-aware placement (speed only; see attn_f16x3_img_kernel): the query tiles of one (sample, head) read the same K / V
-  // rows, so they go to ONE XCD (block w runs on XCD w % 8) and fetch them through the fabric once, not once per tile
-#ifdef CS_ATTN_NO_XCD
-  int bid = blockIdx.x;
-  const int qt = bid % qtiles;
-  bid /= qtiles;
-#else
-  const int xw = blockIdx.x & 7, xj = blockIdx.x >> 3;
-  const int qt = xj % qtiles;
-  const int bid = xw + 8 * (xj / qtiles);
-  if (bid >= nbh) return;                              // grid padded to a multiple of 8 groups (whole workgroup exits)
-#endif
-  const int h = bid % heads;
-  const int b = bid / heads;
+  int qt, b, h;
+  if (!attn_block_map<ATTN_XCD>(qtiles, heads, nbh, qt, b, h)) return;
 
   constexpr int NT = 64 * NW;          // NW waves of 32 queries share each staged K / V tile
   const int q0 = qt * (32 * NW) + wave * 32;
@@ -94,19 +64,8 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
   const float* kb = k + (int64_t)b * nk * ldk + h * dh;
   const float* vb = v + (int64_t)b * nk * ldv + h * dh;
 
-  // Q fragments: qh[t][e] = Q[i][16t + 8*half + e] * scale * QK_SCALE
   h8 qh[KS], ql[KS];
-#pragma unroll
-  for (int t = 0; t < KS; ++t)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int d = 16 * t + 8 * half + e;
-      const float x = d < dh ? qp[d] * (scale * qs) : 0.f;
-      _Float16 a, c;
-      split1m(x, a, c, amax);
-      qh[t][e] = a;
-      ql[t][e] = c;
-    }
+  attn_load_q<KS>(qp, dh, half, scale, qs, qh, ql, amax);
 
   // zero the padding (d >= dh) of the K images and the V^T images once
   for (int u = tid; u < KT * (LDK - dh); u += NT) {
@@ -125,15 +84,9 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
   for (int d = 0; d < DB; ++d)
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
-  // Online softmax in the accumulator's own units: sacc = logit * QK_SCALE^2, so with c = log2(e) / QK_SCALE^2
-  //   p * P_SCALE = exp2((sacc - m) * c + log2(P_SCALE))
-  // is one subtract, one fma and one v_exp_f32 per element (the row maximum m stays in raw units, the P_SCALE the
-  // PV operands need is folded into the exponent, and the running sum carries it until the final normalisation).
   float mrun = -INFINITY;
   float lrun = 0.f;
-  const float cexp = 1.44269504088896340736f / (qs * ks);
-  const float lp = 10.0f;             // log2(P_SCALE)
-  static_assert(P_SCALE == 1024.0f, "lp = log2(P_SCALE)");
+  const AttnExp2 ex = {1.44269504088896340736f / (qs * ks), LOG2_P_SCALE};
 
   // K / V tile staging, software-pipelined: the global loads of tile t+1 are issued (into registers) before tile t's
   // MFMA / softmax work and only converted + written to LDS after it, so their latency never sits between barriers.
@@ -154,7 +107,7 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
     const int vc4 = ok ? u / KT : 0;
     const int vj = ok ? u - vc4 * KT : 0;
     v_g[i] = vj * ldv + vc4 * 4;
-    v_l[i] = ok ? (vc4 * 4) * LDV + vpos(vj) : -1;
+    v_l[i] = ok ? attn_v_off<LDV>(vc4, vj) : -1;
   }
   float4 kr[NU], vr[NU];
   auto load_tile = [&](int kt0) {
@@ -172,26 +125,8 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
   auto store_tile = [&]() {
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
-      if (k_l[i] >= 0) {
-        h4 hi, lo;
-        _Float16 a, c;
-        split1m(kr[i].x * ks, a, c, amax); hi[0] = a; lo[0] = c;
-        split1m(kr[i].y * ks, a, c, amax); hi[1] = a; lo[1] = c;
-        split1m(kr[i].z * ks, a, c, amax); hi[2] = a; lo[2] = c;
-        split1m(kr[i].w * ks, a, c, amax); hi[3] = a; lo[3] = c;
-        *reinterpret_cast<h4*>(Kh + k_l[i]) = hi;
-        if constexpr (!X1) *reinterpret_cast<h4*>(Kl + k_l[i]) = lo;
-      }
-      if (v_l[i] >= 0) {
-        const float x[4] = {vr[i].x, vr[i].y, vr[i].z, vr[i].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          _Float16 a, c;
-          split1m(x[e] * vs, a, c, amax);
-          Vh[v_l[i] + e * LDV] = a;
-          if constexpr (!X1) Vl[v_l[i] + e * LDV] = c;
-        }
-      }
+      if (k_l[i] >= 0) attn_split_k4<X1>(kr[i], ks, Kh, Kl, k_l[i], amax);
+      if (v_l[i] >= 0) attn_split_v4<X1, LDV>(vr[i], vs, Vh, Vl, v_l[i], amax);
     }
   };
   // The prefetch costs 12 * NU registers: worth it while the kernel keeps >= 2 waves per SIMD (DB <= 2: 852 -> 661 us
@@ -211,29 +146,14 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
         const int c4 = u - j * dh4;
         float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (kt0 + j < nk) kv = *reinterpret_cast<const float4*>(kb + (int64_t)(kt0 + j) * ldk + c4 * 4);
-        h4 hi, lo;
-        _Float16 a, c;
-        split1m(kv.x * ks, a, c, amax); hi[0] = a; lo[0] = c;
-        split1m(kv.y * ks, a, c, amax); hi[1] = a; lo[1] = c;
-        split1m(kv.z * ks, a, c, amax); hi[2] = a; lo[2] = c;
-        split1m(kv.w * ks, a, c, amax); hi[3] = a; lo[3] = c;
-        *reinterpret_cast<h4*>(Kh + j * LDK + c4 * 4) = hi;
-        if constexpr (!X1) *reinterpret_cast<h4*>(Kl + j * LDK + c4 * 4) = lo;
+        attn_split_k4<X1>(kv, ks, Kh, Kl, j * LDK + c4 * 4, amax);
       }
       for (int u = tid; u < KT * dh4; u += NT) {          // V: unit = (4 channels, key j), key fastest
         const int c4 = u / KT;
         const int j = u - c4 * KT;
         float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
         if (kt0 + j < nk) vv = *reinterpret_cast<const float4*>(vb + (int64_t)(kt0 + j) * ldv + c4 * 4);
-        const int pj = vpos(j);
-        const float x[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          _Float16 a, c;
-          split1m(x[i] * vs, a, c, amax);
-          Vh[(c4 * 4 + i) * LDV + pj] = a;
-          if constexpr (!X1) Vl[(c4 * 4 + i) * LDV + pj] = c;
-        }
+        attn_split_v4<X1, LDV>(vv, vs, Vh, Vl, attn_v_off<LDV>(c4, j), amax);
       }
     }
     __syncthreads();
@@ -243,113 +163,14 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
     if (PIPE && kt0 + KT < nk) load_tile(kt0 + KT);
 #endif
 
-    // ---- S^T = K Q^T ----
     f32x16 sacc[JB];
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[jb][r] = 0.f;
-#pragma unroll
-    for (int t = 0; t < KS; ++t)
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) {
-        const int off = (jb * 32 + l31) * LDK + 16 * t + 8 * half;
-        const h8 kh = *reinterpret_cast<const h8*>(Kh + off);
-        if constexpr (!X1) {
-          const h8 kl = *reinterpret_cast<const h8*>(Kl + off);
-          sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[t], sacc[jb], 0, 0, 0);
-          sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[t], sacc[jb], 0, 0, 0);
-        }
-        sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[t], sacc[jb], 0, 0, 0);
-      }
-
-    // ---- online softmax (per query i = lane&31) ----
-    if (kt0 + KT > nk) {               // ragged last tile only (wave-uniform): keys past nk take no weight
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = kt0 + jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          if (j >= nk) sacc[jb][r] = -INFINITY;
-        }
-    }
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, sacc[jb][r]);
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    const float mnew = fmaxf(mrun, mloc);
-    const float alpha = (mrun == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mrun - mnew) * cexp);
-    float psum = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-#ifdef CS_ATTN_WHATIF_NO_EXP
-        const float pv = fmaf(sacc[jb][r] - mnew, cexp, lp);
-#else
-        const float pv = __builtin_amdgcn_exp2f(fmaf(sacc[jb][r] - mnew, cexp, lp));   // = p * P_SCALE
-#endif
-        sacc[jb][r] = pv;
-        psum += pv;
-      }
-    lrun = lrun * alpha + psum;
-    mrun = mnew;
-#ifndef CS_ATTN_WHATIF_NO_RESCALE
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-#endif
-
-    // ---- O^T += V^T P^T ----
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        h8 ph, pl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          _Float16 a, c;
-          split1(sacc[jb][8 * qq + e], a, c);
-          ph[e] = a;
-          pl[e] = c;
-        }
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-          const int off = (32 * d + l31) * LDV + 32 * jb + 16 * qq + 8 * half;
-          const h8 vh = *reinterpret_cast<const h8*>(Vh + off);
-          if constexpr (!X1) {
-            const h8 vl = *reinterpret_cast<const h8*>(Vl + off);
-            oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, oacc[d], 0, 0, 0);
-            oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, oacc[d], 0, 0, 0);
-          }
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, oacc[d], 0, 0, 0);
-        }
-      }
+    attn_qk_tile<X1, DB, KT>(Kh, Kl, qh, ql, l31, half, sacc);
+    attn_softmax_tile<KT>(sacc, oacc, mrun, lrun, kt0, nk, half, ex);
+    attn_pv_tile<X1, DB, KT>(Vh, Vl, sacc, l31, half, oacc);
   }
 
   if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
-  const float ltot = lrun + __shfl_xor(lrun, 32, 64);
-  const float inv = 1.0f / (ltot * vs);       // ltot already carries P_SCALE
-  if (q0 + l31 < nq) {
-    float* op = out + ((int64_t)b * nq + q0 + l31) * ldo + h * dh;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = 32 * d + 8 * g + 4 * half;
-        if (dd < dh) {
-          float4 o;
-          o.x = oacc[d][4 * g + 0] * inv;
-          o.y = oacc[d][4 * g + 1] * inv;
-          o.z = oacc[d][4 * g + 2] * inv;
-          o.w = oacc[d][4 * g + 3] * inv;
-          *reinterpret_cast<float4*>(op + dd) = o;
-        }
-      }
-  }
+  attn_store_out<DB>(oacc, lrun, vs, out, b, nq, q0 + l31, ldo, h, dh, half);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -362,26 +183,18 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_kernel(const float* __rest
 // output (tests/test_f16x3_gpu.py).
 // ---------------------------------------------------------------------------------------------------------
 template <int DB, int KT>
-struct AttnImg {
-  static constexpr int DP = 32 * DB, LDK = DP + 8, LDV = KT + 8;
-  static constexpr int TILE_HALVES = 2 * (KT * LDK + DP * LDV);
-  static constexpr int TILE_BYTES = TILE_HALVES * 2;
-  static_assert(TILE_BYTES % 1024 == 0, "whole 1 KB DMA chunks");
-};
-
-template <int DB, int KT>
 __global__ __launch_bounds__(256) void attn_presplit_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                             _Float16* __restrict__ img, int nk, int heads, int dh,
                                                             int ldk, int ldv, int ntiles, int32_t* __restrict__ status,
                                                             float ks, float vs) {
   // ks / vs (r6): the operand pre-scales of K and V (QK_SCALE = 16 by default; static bounds: cs_attn_selfattn_f16x3_ws_scaled)
-  using I = AttnImg<DB, KT>;
-  constexpr int LDK = I::LDK, LDV = I::LDV, DP = I::DP;
+  using I = AttnTile<DB, KT>;
+  constexpr int LDK = I::LDK, LDV = I::LDV;
   extern __shared__ __attribute__((aligned(16))) _Float16 sm[];
   _Float16* Kh = sm;
-  _Float16* Kl = Kh + KT * LDK;
-  _Float16* Vh = Kl + KT * LDK;
-  _Float16* Vl = Vh + DP * LDV;
+  _Float16* Kl = Kh + I::K_HALVES;
+  _Float16* Vh = Kl + I::K_HALVES;
+  _Float16* Vl = Vh + I::V_HALVES;
   const int tid = threadIdx.x;
   int bid = blockIdx.x;
   const int tile = bid % ntiles;
@@ -400,29 +213,14 @@ __global__ __launch_bounds__(256) void attn_presplit_kernel(const float* __restr
     const int c4 = u - j * dh4;
     float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (kt0 + j < nk) kv = *reinterpret_cast<const float4*>(kb + (int64_t)(kt0 + j) * ldk + c4 * 4);
-    h4 hi, lo;
-    _Float16 a, c;
-    split1m(kv.x * ks, a, c, amax); hi[0] = a; lo[0] = c;
-    split1m(kv.y * ks, a, c, amax); hi[1] = a; lo[1] = c;
-    split1m(kv.z * ks, a, c, amax); hi[2] = a; lo[2] = c;
-    split1m(kv.w * ks, a, c, amax); hi[3] = a; lo[3] = c;
-    *reinterpret_cast<h4*>(Kh + j * LDK + c4 * 4) = hi;
-    *reinterpret_cast<h4*>(Kl + j * LDK + c4 * 4) = lo;
+    attn_split_k4<false>(kv, ks, Kh, Kl, j * LDK + c4 * 4, amax);
   }
   for (int u = tid; u < KT * dh4; u += 256) {          // V: unit = (key j, 4 channels) too -- coalesced reads
     const int j = u / dh4;
     const int c4 = u - j * dh4;
     float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (kt0 + j < nk) vv = *reinterpret_cast<const float4*>(vb + (int64_t)(kt0 + j) * ldv + c4 * 4);
-    const int pj = vpos(j);
-    const float x[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      _Float16 a, c;
-      split1m(x[i] * vs, a, c, amax);
-      Vh[(c4 * 4 + i) * LDV + pj] = a;
-      Vl[(c4 * 4 + i) * LDV + pj] = c;
-    }
+    attn_split_v4<false, LDV>(vv, vs, Vh, Vl, attn_v_off<LDV>(c4, j), amax);
   }
   __syncthreads();
   uint4* dst = reinterpret_cast<uint4*>(img + (int64_t)blockIdx.x * I::TILE_HALVES);
@@ -437,16 +235,14 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
                                                                  int dh, int ldq, int ldo, float scale, int qtiles,
                                                                  int ntiles, int nbh, int32_t* __restrict__ status,
                                                                  float qs, float ks, float vs) {
-  using I = AttnImg<DB, KT>;
-  constexpr int DP = I::DP, LDK = I::LDK, LDV = I::LDV;
-  constexpr int JB = KT / 32;
-  constexpr int KS = DP / 16;
+  using I = AttnTile<DB, KT>;
+  constexpr int JB = I::JB, KS = I::KS;
   // LDS: two K slots [Kh | Kl] then two V slots [Vh | Vl].  The K images run ONE TILE AHEAD of the V images: iteration t
   // computes S(t + 1) = K(t + 1) Q^T next to the softmax of S(t) (independent work for the one wave a SIMD holds: MFMA
-  // under VALU) and then O += V(t) P(t); K(t + 2) and V(t + 1) are in flight meanwhile.  Same per-tile operations in the
-  // same order as attn_f16x3_kernel: bit-identical output.
-  constexpr int KBYTES = 4 * KT * LDK, VBYTES = 4 * DP * LDV;
-  static_assert(KBYTES + VBYTES == I::TILE_BYTES && KBYTES % 1024 == 0 && VBYTES % 1024 == 0, "image layout");
+  // under VALU) and then O += V(t) P(t); K(t + 2) and V(t + 1) are in flight meanwhile.  The per-tile operations are
+  // attn_f16x3_kernel's, from the same source in the same order: bit-identical output.
+  constexpr int KBYTES = 4 * I::K_HALVES, VBYTES = 4 * I::V_HALVES;
+  static_assert(KBYTES + VBYTES == I::TILE_BYTES && KBYTES % 1024 == 0 && VBYTES % 1024 == 0, "whole 1 KB DMA chunks");
   constexpr int KCH = KBYTES / 1024, VCH = VBYTES / 1024;      // 1 KB (one wave-wide 16-byte DMA) chunks
   extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
   float amax = 0.f;
@@ -457,23 +253,8 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
   const int l31 = lane & 31;
   const int half = lane >> 5;
 
-  // XCD-aware placement (speed only): block w runs on XCD w % 8, each XCD has its own 4 MB L2, and the query tiles of
-  // one (sample, head) all stream the SAME tile images -- so the j-th block of XCD x takes query tile j % qtiles of group
-  // x + 8 * (j / qtiles): a group's workgroups share one L2 and run side by side (the decoder: 32 query tiles = the 32 CUs
-  // of an XCD).  In launch order every XCD would hold tiles of eight groups at once (77 MB of images against 4 MB of
-  // L2: each workgroup then pulls its 9.6 MB through the fabric, ~5 TB/s chip-wide -- that was the kernel's bound).
-#ifdef CS_ATTN_NO_XCD
-  int bid = blockIdx.x;
-  const int qt = bid % qtiles;
-  bid /= qtiles;
-#else
-  const int xw = blockIdx.x & 7, xj = blockIdx.x >> 3;
-  const int qt = xj % qtiles;
-  const int bid = xw + 8 * (xj / qtiles);
-  if (bid >= nbh) return;                              // grid padded to a multiple of 8 groups (whole workgroup exits)
-#endif
-  const int h = bid % heads;
-  const int b = bid / heads;
+  int qt, b, h;
+  if (!attn_block_map<ATTN_XCD>(qtiles, heads, nbh, qt, b, h)) return;
 
   const int q0 = qt * (32 * NW) + wave * 32;
   const int qi = min(q0 + l31, nq - 1);
@@ -505,17 +286,7 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
   dma_v(0);
 
   h8 qh[KS], ql[KS];
-#pragma unroll
-  for (int t = 0; t < KS; ++t)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int d = 16 * t + 8 * half + e;
-      const float x = d < dh ? qp[d] * (scale * qs) : 0.f;
-      _Float16 a, c;
-      split1m(x, a, c, amax);
-      qh[t][e] = a;
-      ql[t][e] = c;
-    }
+  attn_load_q<KS>(qp, dh, half, scale, qs, qh, ql, amax);
 
   f32x16 oacc[DB];
 #pragma unroll
@@ -524,25 +295,24 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
     for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
   float mrun = -INFINITY;
   float lrun = 0.f;
-  const float cexp = 1.44269504088896340736f / (qs * ks);
-  const float lp = 10.0f;             // log2(P_SCALE)
+  const AttnExp2 ex = {1.44269504088896340736f / (qs * ks), LOG2_P_SCALE};
 
   // S^T = K Q^T of tile t (its K image sits in K slot t & 1)
   auto qk = [&](int t, f32x16 (&sacc)[JB]) {
     const _Float16* Kh = reinterpret_cast<const _Float16*>(smb + (t & 1) * KBYTES);
-    const _Float16* Kl = Kh + KT * LDK;
+    const _Float16* Kl = Kh + I::K_HALVES;
+#if CS_ATTN_RING
 #pragma unroll
     for (int jb = 0; jb < JB; ++jb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) sacc[jb][r] = 0.f;
-#if CS_ATTN_RING
     // fragment reads RING steps ahead of their MFMAs; the scheduling fences keep the compiler from sinking every read
     // next to its use (at 512 live registers it minimises live ranges: read -> wait -> MFMA, the whole LDS latency exposed)
     constexpr int NS = KS * JB;
     h8 ah[RING], al[RING];
     auto ld = [&](int st, int slot) {
       const int tt = st / JB, jb = st - tt * JB;
-      const int off = (jb * 32 + l31) * LDK + 16 * tt + 8 * half;
+      const int off = (jb * 32 + l31) * I::LDK + 16 * tt + 8 * half;
 #ifdef CS_ATTN_WHATIF_NO_LDSREAD
       ah[slot] = qh[tt]; al[slot] = ql[tt]; (void)off;
 #else
@@ -564,17 +334,7 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
     }
     __builtin_amdgcn_sched_barrier(0);
 #else
-#pragma unroll
-    for (int tt = 0; tt < KS; ++tt)
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb) {
-        const int off = (jb * 32 + l31) * LDK + 16 * tt + 8 * half;
-        const h8 kh = *reinterpret_cast<const h8*>(Kh + off);
-        const h8 kl = *reinterpret_cast<const h8*>(Kl + off);
-        sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[tt], sacc[jb], 0, 0, 0);
-        sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[tt], sacc[jb], 0, 0, 0);
-        sacc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[tt], sacc[jb], 0, 0, 0);
-      }
+    attn_qk_tile<false, DB, KT>(Kh, Kl, qh, ql, l31, half, sacc);
 #endif
   };
 
@@ -596,49 +356,11 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
 #endif
     if (t + 1 < ntiles) qk(t + 1, snext);
 
-    // ---- online softmax of tile t (per query i = lane&31) ----
-    if (kt0 + KT > nk) {               // ragged last tile only (wave-uniform): keys past nk take no weight
-#pragma unroll
-      for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = kt0 + jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          if (j >= nk) scur[jb][r] = -INFINITY;
-        }
-    }
-    float mloc = -INFINITY;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, scur[jb][r]);
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-    const float mnew = fmaxf(mrun, mloc);
-    const float alpha = (mrun == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mrun - mnew) * cexp);
-    float psum = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-#ifdef CS_ATTN_WHATIF_NO_EXP           // (timing-only what-if build: wrong results)
-        const float pv = fmaf(scur[jb][r] - mnew, cexp, lp);
-#else
-        const float pv = __builtin_amdgcn_exp2f(fmaf(scur[jb][r] - mnew, cexp, lp));   // = p * P_SCALE
-#endif
-        scur[jb][r] = pv;
-        psum += pv;
-      }
-    lrun = lrun * alpha + psum;
-    mrun = mnew;
-#ifndef CS_ATTN_WHATIF_NO_RESCALE      // (timing-only what-if build: wrong results)
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-#endif
+    attn_softmax_tile<KT>(scur, oacc, mrun, lrun, kt0, nk, half, ex);      // of tile t
 
     // ---- O^T += V(t)^T P^T ----
     const _Float16* Vh = reinterpret_cast<const _Float16*>(smb + 2 * KBYTES + (t & 1) * VBYTES);
-    const _Float16* Vl = Vh + DP * LDV;
+    const _Float16* Vl = Vh + I::V_HALVES;
 #if CS_ATTN_RING
     {
       constexpr int NS = JB * 2 * DB;                    // step = ((jb, qq), d)
@@ -655,7 +377,7 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
       h8 ah[RING], al[RING];
       auto ld = [&](int st, int slot) {
         const int g = st / DB, d = st - g * DB;
-        const int off = (32 * d + l31) * LDV + 32 * (g >> 1) + 16 * (g & 1) + 8 * half;
+        const int off = (32 * d + l31) * I::LDV + 32 * (g >> 1) + 16 * (g & 1) + 8 * half;
 #ifdef CS_ATTN_WHATIF_NO_LDSREAD
         ah[slot] = qh[d]; al[slot] = ql[d]; (void)off;
 #else
@@ -678,69 +400,26 @@ __global__ __launch_bounds__(64 * NW) void attn_f16x3_img_kernel(const float* __
       __builtin_amdgcn_sched_barrier(0);
     }
 #else
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        h8 ph, pl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          _Float16 a, c;
-          split1(scur[jb][8 * qq + e], a, c);
-          ph[e] = a;
-          pl[e] = c;
-        }
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-          const int off = (32 * d + l31) * LDV + 32 * jb + 16 * qq + 8 * half;
-          const h8 vh = *reinterpret_cast<const h8*>(Vh + off);
-          const h8 vl = *reinterpret_cast<const h8*>(Vl + off);
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, oacc[d], 0, 0, 0);
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, oacc[d], 0, 0, 0);
-          oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, oacc[d], 0, 0, 0);
-        }
-      }
+    attn_pv_tile<false, DB, KT>(Vh, Vl, scur, l31, half, oacc);
 #endif
 #pragma unroll
     for (int jb = 0; jb < JB; ++jb) scur[jb] = snext[jb];
   }
 
   if (status && amax >= 65504.f) atomicOr(status, CS_STATUS_F16X3_OVERFLOW);
-  const float ltot = lrun + __shfl_xor(lrun, 32, 64);
-  const float inv = 1.0f / (ltot * vs);       // ltot already carries P_SCALE
-  if (q0 + l31 < nq) {
-    float* op = out + ((int64_t)b * nq + q0 + l31) * ldo + h * dh;
-#pragma unroll
-    for (int d = 0; d < DB; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = 32 * d + 8 * g + 4 * half;
-        if (dd < dh) {
-          float4 o;
-          o.x = oacc[d][4 * g + 0] * inv;
-          o.y = oacc[d][4 * g + 1] * inv;
-          o.z = oacc[d][4 * g + 2] * inv;
-          o.w = oacc[d][4 * g + 3] * inv;
-          *reinterpret_cast<float4*>(op + dd) = o;
-        }
-      }
-  }
+  attn_store_out<DB>(oacc, lrun, vs, out, b, nq, q0 + l31, ldo, h, dh, half);
 }
 
 template <int DB, int KT, int NW>
 int launch_attn16_img(const float* q, const float* k, const float* v, float* out, int nb, int nq, int nk, int heads,
                       int dh, int ldq, int ldk, int ldv, int ldo, float scale, int32_t* status, void* ws, hipStream_t s,
-                      float qs = QK_SCALE, float ks = QK_SCALE, float vs = QK_SCALE) {
-  using I = AttnImg<DB, KT>;
+                      float qs, float ks, float vs) {
+  using I = AttnTile<DB, KT>;
   const int ntiles = (nk + KT - 1) / KT;
   if ((int64_t)ntiles * I::TILE_BYTES >= 0x7FF00000LL) return CS_EINVAL;
   const int64_t pgrid = (int64_t)nb * heads * ntiles;
   const int qtiles = (nq + 32 * NW - 1) / (32 * NW);
-#ifdef CS_ATTN_NO_XCD
-  const int64_t grid = (int64_t)qtiles * heads * nb;
-#else
-  const int64_t grid = (int64_t)qtiles * (((int64_t)heads * nb + 7) / 8 * 8);      // whole groups of eight (sample, head)s
-#endif
+  const int64_t grid = attn_grid<ATTN_XCD>(qtiles, nb, heads);
   if (pgrid > 0x7fffffffLL || grid > 0x7fffffffLL) return CS_EINVAL;
   auto pk = attn_presplit_kernel<DB, KT>;
   auto kern = attn_f16x3_img_kernel<DB, KT, NW>;
@@ -776,15 +455,10 @@ inline int img_variant(int nq, int nk, int dh) {
 template <int DB, int KT, bool X1, int NW = 4>
 int launch_attn16(const float* q, const float* k, const float* v, float* out, int nb, int nq, int nk, int heads,
                   int dh, int ldq, int ldk, int ldv, int ldo, float scale, int32_t* status, hipStream_t s,
-                  float qs = QK_SCALE, float ks = QK_SCALE, float vs = QK_SCALE) {
-  constexpr int DP = 32 * DB;
-  const size_t smem = (size_t)(2 * KT * (DP + 8) + 2 * DP * (KT + 8)) * sizeof(_Float16);
+                  float qs, float ks, float vs) {
+  const size_t smem = AttnTile<DB, KT>::TILE_BYTES;
   const int qtiles = (nq + 32 * NW - 1) / (32 * NW);
-#ifdef CS_ATTN_NO_XCD
-  const int64_t grid = (int64_t)qtiles * heads * nb;
-#else
-  const int64_t grid = (int64_t)qtiles * (((int64_t)heads * nb + 7) / 8 * 8);      // whole groups of eight (sample, head)s
-#endif
+  const int64_t grid = attn_grid<ATTN_XCD>(qtiles, nb, heads);
   if (grid > 0x7fffffffLL) return CS_EINVAL;
   auto kern = attn_f16x3_kernel<DB, KT, X1, NW>;
   if (smem > 64 * 1024) {
@@ -799,16 +473,19 @@ int launch_attn16(const float* q, const float* k, const float* v, float* out, in
 
 }  // namespace
 
+// The ONE implementation behind the five fp16-MFMA entries below (X1 = cs_attn_selfattn_f16).  qs / ks / vs = the operands' power-of-two pre-scales
+// (QK_SCALE each unless the caller gives its own); ws = the tile-image workspace or NULL: it is used -- and checked -- only
+// where img_variant takes the shape, and ignored, alignment included, everywhere else.
 template <bool X1>
-static int attn16_dispatch(const float* q, const float* k, const float* v, float* out, int nb, int nq, int nk, int heads,
-                           int dh, int ldq, int ldk, int ldv, int ldo, float scale, int32_t* status, cs_stream_t stream,
-                           float qs = QK_SCALE, float ks = QK_SCALE, float vs = QK_SCALE) {
-  if (!q || !k || !v || !out || nb <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || dh <= 0) return CS_EINVAL;
-  if ((dh & 3) || (ldq & 3) || (ldk & 3) || (ldv & 3) || (ldo & 3)) return CS_EINVAL;
-  if (ldq < heads * dh || ldk < heads * dh || ldv < heads * dh || ldo < heads * dh) return CS_EINVAL;
-  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15))
-    return CS_EINVAL;
+static int attn16_run(const float* q, const float* k, const float* v, float* out, int nb, int nq, int nk, int heads, int dh,
+                      int ldq, int ldk, int ldv, int ldo, float scale, int32_t* status, void* ws, cs_stream_t stream,
+                      float qs = QK_SCALE, float ks = QK_SCALE, float vs = QK_SCALE) {
+  if (!(qs > 0.f) || !(ks > 0.f) || !(vs > 0.f)) return CS_EINVAL;      // (NaN included) before anything else
+  const int var = (ws && !X1) ? img_variant(nq, nk, dh) : 0;
+  if (!attn_args_ok(q, k, v, out, var ? ws : nullptr, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo)) return CS_EINVAL;
   hipStream_t s = (hipStream_t)stream;
+  if (var == 8)
+    return launch_attn16_img<8, 32, 4>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, ws, s, qs, ks, vs);
   if (dh <= 32) return launch_attn16<1, 64, X1>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, s, qs, ks, vs);
   // eight waves per staged tile amortise the K / V conversion over 256 queries -- but only once such workgroups fill the
   // chip: at small batches (1 object: 16 (sample, head) groups, 64 workgroups at 1024 tokens, 16 at 256) four-wave
@@ -838,7 +515,7 @@ static int attn16_dispatch(const float* q, const float* k, const float* v, float
 extern "C" int cs_attn_selfattn_f16x3(const float* q, const float* k, const float* v, float* out, int nb, int nq,
                                       int nk, int heads, int dh, int ldq, int ldk, int ldv, int ldo, float scale,
                                       int32_t* status, cs_stream_t stream) {
-  return attn16_dispatch<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, stream);
+  return attn16_run<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, nullptr, stream);
 }
 
 // r5: the same kernel with the operands' power-of-two pre-scales given by the caller instead of the constant 16: a
@@ -850,15 +527,14 @@ extern "C" int cs_attn_selfattn_f16x3_scaled(const float* q, const float* k, con
                                              int nk, int heads, int dh, int ldq, int ldk, int ldv, int ldo, float scale,
                                              float q_scale, float k_scale, float v_scale, int32_t* status,
                                              cs_stream_t stream) {
-  if (!(q_scale > 0.f) || !(k_scale > 0.f) || !(v_scale > 0.f)) return CS_EINVAL;
-  return attn16_dispatch<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, stream, q_scale,
-                                k_scale, v_scale);
+  return attn16_run<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, nullptr, stream, q_scale,
+                           k_scale, v_scale);
 }
 
 extern "C" int cs_attn_selfattn_f16(const float* q, const float* k, const float* v, float* out, int nb, int nq,
                                     int nk, int heads, int dh, int ldq, int ldk, int ldv, int ldo, float scale,
                                     int32_t* status, cs_stream_t stream) {
-  return attn16_dispatch<true>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, stream);
+  return attn16_run<true>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, nullptr, stream);
 }
 
 // Workspace form of cs_attn_selfattn_f16x3: with `ws` (cs_attn_f16x3_ws_bytes(...) bytes, 16-byte aligned) K and V are
@@ -868,30 +544,14 @@ extern "C" int cs_attn_selfattn_f16(const float* q, const float* k, const float*
 extern "C" int64_t cs_attn_f16x3_ws_bytes(int nb, int nq, int nk, int heads, int dh) {
   if (nb <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || dh <= 0) return 0;
   const int var = img_variant(nq, nk, dh);
-  if (var == 8) return (int64_t)nb * heads * ((nk + 31) / 32) * AttnImg<8, 32>::TILE_BYTES;
+  if (var == 8) return (int64_t)nb * heads * ((nk + 31) / 32) * AttnTile<8, 32>::TILE_BYTES;
   return 0;
-}
-
-static int attn_ws_impl(const float* q, const float* k, const float* v, float* out, int nb, int nq,
-                       int nk, int heads, int dh, int ldq, int ldk, int ldv, int ldo, float scale,
-                       int32_t* status, void* ws, cs_stream_t stream, float qs, float ks, float vs) {
-  const int var = ws ? img_variant(nq, nk, dh) : 0;
-  if (var == 0)
-    return attn16_dispatch<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, stream, qs, ks, vs);
-  if (!q || !k || !v || !out || nb <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || dh <= 0) return CS_EINVAL;
-  if ((dh & 3) || (ldq & 3) || (ldk & 3) || (ldv & 3) || (ldo & 3)) return CS_EINVAL;
-  if (ldq < heads * dh || ldk < heads * dh || ldv < heads * dh || ldo < heads * dh) return CS_EINVAL;
-  if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15) || ((uintptr_t)out & 15) || ((uintptr_t)ws & 15))
-    return CS_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  return launch_attn16_img<8, 32, 4>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, ws, s, qs, ks, vs);
 }
 
 extern "C" int cs_attn_selfattn_f16x3_ws(const float* q, const float* k, const float* v, float* out, int nb, int nq,
                                          int nk, int heads, int dh, int ldq, int ldk, int ldv, int ldo, float scale,
                                          int32_t* status, void* ws, cs_stream_t stream) {
-  return attn_ws_impl(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, ws, stream, QK_SCALE, QK_SCALE,
-                      QK_SCALE);
+  return attn16_run<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, ws, stream);
 }
 
 // r6 (ABI 18): the workspace form with the caller's operand pre-scales (see cs_attn_selfattn_f16x3_scaled) -- what an
@@ -902,7 +562,6 @@ extern "C" int cs_attn_selfattn_f16x3_ws_scaled(const float* q, const float* k, 
                                                 int nk, int heads, int dh, int ldq, int ldk, int ldv, int ldo, float scale,
                                                 float q_scale, float k_scale, float v_scale, int32_t* status, void* ws,
                                                 cs_stream_t stream) {
-  if (!(q_scale > 0.f) || !(k_scale > 0.f) || !(v_scale > 0.f)) return CS_EINVAL;
-  return attn_ws_impl(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, ws, stream, q_scale, k_scale,
-                      v_scale);
+  return attn16_run<false>(q, k, v, out, nb, nq, nk, heads, dh, ldq, ldk, ldv, ldo, scale, status, ws, stream, q_scale,
+                           k_scale, v_scale);
 }
