@@ -100,6 +100,38 @@ __device__ __forceinline__ cs_u32x4 cs_pair16_half32(const f32x4& v, float out_s
   r[3] = s1[1];
   return r;
 }
+// Whole-line stores from a TRANSPOSED 32x32 MFMA accumulator (cs_gemm_f16x3.hip, TR kernels).  There lane (r = l & 31,
+// h = l >> 5) holds in x[g] the columns 8 g + 4 h + 0..3 of row r of the block: a store of x[g] touches 32 rows with 32 bytes
+// each.  The four lanes of a quad (rows r0 + q, q = l & 3, same h) exchange their float4s -- a 4x4 transposition of float4s --
+// so that x[s] of lane q becomes row r0 + s, columns 8 q + 4 h + 0..3: the store of slot s then covers eight rows with one whole
+// 128-byte line of the block each (q = 0..3, h = 0..1 of a quad pair are one row's 32 columns), and a residual loaded at those
+// addresses does too.  Two butterfly steps of DPP quad_perm moves (partner q ^ 1 swaps the odd / even slots, partner q ^ 2 the
+// upper / lower pair); registers only, no LDS, no barrier, one block at a time.  PRECONDITION: the whole wave is active (a DPP
+// move reads nothing from a lane EXEC masks out).  Values are moved, never changed: lanes l / l + 32 still hold the two halves
+// of one row's eight columns afterwards, which is what cs_pair16_half32 asks for.
+__device__ __forceinline__ void cs_quad_transpose4(f32x4 (&x)[4], int lane) {
+  const bool o1 = lane & 1, o2 = lane & 2;
+#pragma unroll
+  for (int s = 0; s < 4; s += 2)       // slot bit 0 <-> lane bit 0 (quad_perm 1,0,3,2)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = x[s][e], b = x[s + 1][e];
+      const float recv = __builtin_bit_cast(
+          float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, o1 ? a : b), 0xB1, 0xF, 0xF, true));
+      x[s][e] = o1 ? recv : a;
+      x[s + 1][e] = o1 ? b : recv;
+    }
+#pragma unroll
+  for (int s = 0; s < 2; ++s)          // slot bit 1 <-> lane bit 1 (quad_perm 2,3,0,1)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = x[s][e], b = x[s + 2][e];
+      const float recv = __builtin_bit_cast(
+          float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, o2 ? a : b), 0x4E, 0xF, 0xF, true));
+      x[s][e] = o2 ? recv : a;
+      x[s + 2][e] = o2 ? b : recv;
+    }
+}
 __device__ __forceinline__ int cs_pair_off(int col) { return (col >> 4) * 64 + ((col & 8) ? 32 : 0) + ((col & 4) ? 16 : 0); }
 // a converted value reached the fp16 range (its hi half would be +-inf): the sticky flag of the launch
 template <class D>

@@ -23,17 +23,21 @@
 // + halo, so they hit L1/L2 instead of re-streaming the activation tensor per tap).
 // fp16 32x32x16 operand map: lane l holds row/col l&31 and k = 8*(l>>5) .. 8*(l>>5)+7; C/D as for fp32: lane l holds
 // column l&31 and rows (r&3) + 8*(r>>2) + 4*(l>>5) of the block in register r.
-// TR (the pointwise instantiations): both operands have that one fragment shape, so the K loop passes them SWAPPED --
+// TR (the pointwise instantiations and the three-tap Winograd-W position GEMMs): both operands have that one fragment shape, so
+// the K loop passes them SWAPPED --
 // mfma(b_frag, a_frag) -- and the block comes out transposed at no cost: lane l holds output ROW l&31, and registers
 // 4g .. 4g+3 are the four consecutive columns 8g + 4*(l>>5) + 0..3 of block j, a float4 of the row.  The same exact
 // products are summed over the same k: the bits do not change.
 // Epilogues.  Untransposed kernels stage the accumulators through the idle ring (a lane owns a column, stores want rows): the
 // pipelined path (bias / row-vector rows and the next pass's residual rows LDS-DMA'd), the plain float4 path, the scalar one.
-// TR kernels store straight from registers where the pipelined path would serve and no GroupNorm partials are asked for: the
-// residual float4s are loaded at the store addresses in one or two batches, bias and row vector come from an LDS area the
-// prologue fills beyond the ring, GEGLU pairs column c with c + WCOLS/2 of the same lane, the pair output exchanges halves
-// across lanes l / l+32 (cs_epilogue.h::cs_pair16_half32); no staging, no barrier.  Everything else on a TR kernel first
-// puts the blocks back into the untransposed layout through LDS and then runs the code of the other kernels unchanged.
+// TR kernels store straight from registers where the pipelined path would serve and no GroupNorm partials are asked for: bias
+// and row vector come from an LDS area the prologue fills beyond the ring, GEGLU pairs column c with c + WCOLS/2 of the same
+// lane; on the tiles that run one workgroup per CU (`LINE` in the kernel) the finished float4s of each block are then
+// transposed inside the lane quads (cs_epilogue.h::cs_quad_transpose4), so that one store instruction covers eight rows x a
+// whole 128-byte line instead of 32 rows x 32 bytes; the residual float4s are loaded at the store addresses in one or two
+// batches, and the pair output exchanges halves across lanes l / l+32 (cs_pair16_half32); no staging, no barrier.  A position GEMM's tile has no terms: transposition, then the stores into its
+// workspace rows, K slices included.  Everything else on a TR kernel first puts the blocks back into the untransposed layout
+// through LDS and then runs the code of the other kernels unchanged.
 #include <cstdlib>
 #include <cstring>
 #include "cs_f16x3.h"
@@ -257,7 +261,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
   constexpr int NT = 64 * NW;
   // TR: the pointwise kernels accumulate the TRANSPOSED product (operand map in the file header): a lane then owns float4s of
   // one output row, and the epilogue stores from registers.  Derived, not a template argument: the launch table is unchanged.
-  constexpr bool TR = PW;
+  // The Winograd-W position GEMMs (TPK == 3) too: their tiles go to the workspace with no epilogue term at all.
+  // LINE: the register-direct epilogue first transposes float4s inside lane quads (cs_epilogue.h::cs_quad_transpose4), so every
+  // store and residual-load instruction covers whole 128-byte lines.  Kept where it was measured to gain: the
+  // position GEMMs and the 256x224 pointwise tile, one workgroup per CU each, so nothing overlaps their epilogue.  The other
+  // pointwise tiles run two workgroups per CU; there the lines saved did not pay for the exchange and its registers (128x224,
+  // pair operand: +0.07 ms per step), and they keep the row-per-lane stores.
+  // A/B builds: -DCS_LINE_POS=0 = the position GEMMs untransposed with the staged epilogue; -DCS_LINE_PW=0 / 2 = no / every
+  // pointwise tile with line stores.
+#ifndef CS_LINE_POS
+#define CS_LINE_POS 1
+#endif
+#ifndef CS_LINE_PW
+#define CS_LINE_PW 1
+#endif
+  constexpr bool TR = PW || (TPK == 3 && CS_LINE_POS);
+  constexpr bool LINE = TPK == 3 || CS_LINE_PW == 2 || (CS_LINE_PW == 1 && BM == 256 && BN == 224);
   // ---- LDS map (bytes) ----
   static_assert(!SLAB || (WMB <= 2 && WAVES_N == 1), "slab path: one or two row blocks per wave");
   static_assert(!PAIR || (!PRE && SLAB == 0), "interleaved operand pairs: per-tap gather path only");
@@ -586,8 +605,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
   // TR: the tile's bias row and the row-vector row of its FIRST sample go to the (pointwise: unused) row-table area beyond the
   // ring BEFORE the first chunk's DMAs -- the oldest transfers in flight, so the prologue's counted wait and barrier cover
   // them and no vmcnt of the K loop changes; the register-direct epilogue reads them without waiting for the ring to drain.
+  // (pointwise only: a position GEMM's register-direct epilogue has no terms, and on the slab kernels that area holds the zero
+  // block of the masked taps)
   constexpr int TRV = ROWBASE;                     // float [256] bias row, float [256] row-vector row
-  if constexpr (TR) {
+  if constexpr (PW) {
     static_assert(TRV + 2048 <= LDS_BYTES && BN <= 256 && (BN + 63) / 64 <= NW, "bias / row-vector rows beyond the ring");
     if (wave < (BN + 63) / 64) {                   // 4 bytes per lane; columns past cout read zero
       const unsigned col = (unsigned)(64 * wave + lane);
@@ -868,9 +889,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
       }
 #pragma unroll
       for (int i = 0; i < WMB; ++i) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+        if constexpr (TR) {            // (the position GEMMs: operands swapped as in `step`, the block comes out transposed)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al[i], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah[i], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah[i], acc[i][j], 0, 0, 0);
+        } else {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
+        }
       }
       if (j == 0) {
         if constexpr (t9 == 0) issue_slab(sc + 1);       // its buffer was last read while chunk k-2 was computed
@@ -1042,6 +1069,201 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
       // of the row.  No LDS staging, no barrier: the residual float4s of a batch of column groups are loaded at the store
       // addresses, all at once, the bias / row-vector float4s come from the area the prologue filled, and every element
       // takes the operations of cs_epi_terms4 in its order -- the bits of the staged paths.
+      // LINE: each finished block of four float4s is transposed inside the lane quads first (cs_quad_transpose4): slot s of
+      // lane (q = l31 & 3, half) is then row (l31 & ~3) + s, columns 8 q + 4 half + 0..3 of the block, and every store / residual
+      // load instruction covers eight rows x one whole 128-byte line.  Row validity is per slot, column validity per lane.
+      const int q4 = l31 & 3, r4 = l31 & ~3;
+      if constexpr (TPK == 3) {
+        // ---- the Winograd-W position GEMMs: the tile, times acc_scale, straight into its rows of the workspace
+        // [slices][P][M / R][cout] -- unsliced, K-sliced and tail-plan launches alike (the slice is `outp`'s offset and nothing
+        // else).  No term, no staging, no barrier.  A launch of this kernel that does carry epilogue terms is not a position
+        // launch of conv_wino: it untransposes below and runs the other kernels' code.
+        const bool bare = !p.bias && !p.scale && !p.rowvec && !p.res && p.act == CS_ACT_NONE && !gstat && !opair;
+        if (!(CS_ABLATE & 32) && vec_epilogue && bare && (long long)BM * p.ldo * 4 < 0x7FF00000LL) {
+          typedef cs_u32x4 u32x4;
+          const int rows = min(BM, M - m0);
+          const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
+              (void*)(outp + (int64_t)m0 * p.ldo), 0, (unsigned)(((int64_t)(rows - 1) * p.ldo + p.cout) * 4), 0x00020000);
+          const int cq = n0 + wn0 + 8 * q4 + 4 * half;         // the lane's column of block 0
+#pragma unroll
+          for (int i = 0; i < WMB; ++i) {
+            const int row0 = wm0 + 32 * i + r4;                // slot 0's row of the tile
+            const unsigned orow = (unsigned)(row0 * p.ldo) * 4u;
+#pragma unroll
+            for (int j = 0; j < WNB; ++j) {
+              f32x4 v[4];
+#pragma unroll
+              for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[g][e] = acc[i][j][4 * g + e] * acc_scale_;
+              cs_quad_transpose4(v, lane);
+              const int n = cq + 32 * j;
+#pragma unroll
+              for (int s = 0; s < 4; ++s) {
+                unsigned off = (row0 + s < rows && n < p.cout) ? orow + (unsigned)(s * p.ldo + n) * 4u : OOB;
+                if (CS_ABLATE & 16384) off = OOB;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[s]), ors, off, 0, 0);
+              }
+            }
+          }
+          return;
+        }
+      }
+      if constexpr (PW && LINE) {
+      if (piped && !gstat) {
+        typedef cs_u32x4 u32x4;
+        constexpr int JB = (4 * WMB * WNB <= 16) ? WNB : 4 / WMB;      // blocks per residual batch: at most 16 float4s in flight
+        static_assert(JB >= 1 && 4 * WMB * JB <= 16, "residual batches");
+        const long long o_skip = (long long)m0 * p.ldo * 4, r_skip = (long long)m0 * p.ldr * 4;
+        const long long o_cols = geglu ? p.cout / 2 : p.cout;
+        const long long o_left = ((long long)(M - 1) * p.ldo + o_cols) * 4 - o_skip;
+        const long long r_left = has_res ? ((long long)(M - 1) * p.ldr + p.cout) * 4 - r_skip : 0;
+        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)((char*)p.out + o_skip), 0, o_left > 0x7FF00000LL ? 0x7FF00000u : (unsigned)o_left, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(has_res ? (const char*)p.res + r_skip : (const char*)p.out), 0,
+            r_left > 0x7FF00000LL ? 0x7FF00000u : (r_left > 0 ? (unsigned)r_left : 0u), 0x00020000);
+        // bias / row vector: added BEFORE the transposition, where a lane's column is that of its half-wave
+        const float* const tvb = reinterpret_cast<const float*>(smem + TRV) + wn0 + 4 * half;
+        const float* const tvr = tvb + 256;
+        int nrow[WMB];                                         // valid rows from slot 0's on: slot s holds one iff s < nrow
+        unsigned orow[WMB], rrow[WMB];
+#pragma unroll
+        for (int i = 0; i < WMB; ++i) {
+          const int row0 = wm0 + 32 * i + r4;
+          nrow[i] = M - m0 - row0;
+          orow[i] = (unsigned)(row0 * p.ldo) * 4u;
+          rrow[i] = (unsigned)(row0 * p.ldr) * 4u;
+        }
+        const unsigned ostep = (unsigned)p.ldo * 4u, rstep = (unsigned)p.ldr * 4u;
+        float oamax = 0.f;
+        if (geglu) {
+          // columns of the wave = [x (WCOLS/2) | gate (WCOLS/2)]: the partner of group t is group t + NG/2 of the same lane.  The
+          // HG finished float4s of a row are transposed four at a time (the last set may hold fewer: its other lanes are masked)
+          constexpr int HG = 2 * WNB;
+          const int co = (n0 + wn0) / 2 + 8 * q4 + 4 * half;   // output column of the lane in set 0
+#pragma unroll
+          for (int b = 0; b < (HG + 3) / 4; ++b) {
+            f32x4 bx[4], bg[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              bx[g] = bg[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+              if (4 * b + g < HG && p.bias) {
+                bx[g] = *reinterpret_cast<const f32x4*>(tvb + 8 * (4 * b + g));
+                bg[g] = *reinterpret_cast<const f32x4*>(tvb + 8 * (4 * b + g + HG));
+              }
+            }
+            const bool cok = 4 * b + q4 < HG;                  // (whole [x | gate] groups: no column past cout)
+#pragma unroll
+            for (int i = 0; i < WMB; ++i) {
+              f32x4 v[4];
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                v[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                const int t = 4 * b + g;
+                if (t < HG) {                                  // (compile time)
+                  f32x4 xv, gv;
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) {
+                    xv[e] = acc[i][t / 4][4 * (t % 4) + e] * acc_scale_;
+                    gv[e] = acc[i][(t + HG) / 4][4 * ((t + HG) % 4) + e] * acc_scale_;
+                  }
+                  if (p.bias) {
+                    xv += bx[g];
+                    gv += bg[g];
+                  }
+                  v[g] = (CS_ABLATE & 32768) ? xv * gv : cs_geglu4(xv, gv);
+                }
+              }
+              cs_quad_transpose4(v, lane);
+#pragma unroll
+              for (int s = 0; s < 4; ++s) {
+                const bool ok = cok && s < nrow[i];
+                if (opair) {
+                  if (!ok) v[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+                  const u32x4 pk = cs_pair16_half32(v[s], p.out_scale, oamax);
+                  unsigned off = ok ? orow[i] + (unsigned)s * ostep + (unsigned)cs_pair_off(co + 32 * b) : OOB;
+                  if (CS_ABLATE & 16384) off = OOB;
+                  __builtin_amdgcn_raw_buffer_store_b128(pk, ors, off, 0, 0);
+                } else {
+                  unsigned off = ok ? orow[i] + (unsigned)s * ostep + (unsigned)(co + 32 * b) * 4u : OOB;
+                  if (CS_ABLATE & 16384) off = OOB;
+                  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[s]), ors, off, 0, 0);
+                }
+              }
+            }
+          }
+        } else {
+          const int cq = n0 + wn0 + 8 * q4 + 4 * half;         // the lane's column of block 0 after the transposition
+#pragma unroll
+          for (int j0 = 0; j0 < WNB; j0 += JB) {
+            f32x4 rv[WMB][JB][4];
+            if (has_res) {                                     // at the transposed addresses: whole lines too
+#pragma unroll
+              for (int i = 0; i < WMB; ++i)
+#pragma unroll
+                for (int jj = 0; jj < JB; ++jj)
+#pragma unroll
+                  for (int s = 0; s < 4; ++s) {
+                    if (j0 + jj >= WNB) continue;              // (compile time)
+                    const int n = cq + 32 * (j0 + jj);
+                    const unsigned off = (s < nrow[i] && n < p.cout) ? rrow[i] + (unsigned)s * rstep + (unsigned)n * 4u : OOB;
+                    rv[i][jj][s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrs, off, 0, 0));
+                  }
+            }
+#pragma unroll
+            for (int jj = 0; jj < JB; ++jj) {
+              const int j = j0 + jj;
+              if (j >= WNB) continue;                          // (compile time)
+              f32x4 bv[4], vv[4];
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                bv[g] = vv[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (p.bias) bv[g] = *reinterpret_cast<const f32x4*>(tvb + 32 * j + 8 * g);
+                if (p.rowvec) vv[g] = *reinterpret_cast<const f32x4*>(tvr + 32 * j + 8 * g);
+              }
+              const int n = cq + 32 * j;
+#pragma unroll
+              for (int i = 0; i < WMB; ++i) {
+                f32x4 v[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) v[g][e] = acc[i][j][4 * g + e] * acc_scale_;
+                  if (p.bias) v[g] += bv[g];
+                  if (p.rowvec) v[g] += vv[g];
+                  if (p.act != CS_ACT_NONE) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[g][e] = cs_act(v[g][e], p.act);
+                  }
+                }
+                cs_quad_transpose4(v, lane);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                  if (has_res) v[s] += rv[i][jj][s];
+                  const bool ok = s < nrow[i] && n < p.cout;
+                  if (opair) {
+                    if (!ok) v[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const u32x4 pk = cs_pair16_half32(v[s], p.out_scale, oamax);
+                    unsigned off = ok ? orow[i] + (unsigned)s * ostep + (unsigned)cs_pair_off(n) : OOB;
+                    if (CS_ABLATE & 16384) off = OOB;
+                    __builtin_amdgcn_raw_buffer_store_b128(pk, ors, off, 0, 0);
+                  } else {
+                    unsigned off = ok ? orow[i] + (unsigned)s * ostep + (unsigned)n * 4u : OOB;
+                    if (CS_ABLATE & 16384) off = OOB;
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[s]), ors, off, 0, 0);
+                  }
+                }
+              }
+            }
+          }
+        }
+        cs_pair_flag(p, opair, oamax);
+        return;
+      }
+      }
+      // (-DCS_LINE_PW=0: the row-per-lane form -- a lane stores float4s of its own row, 32 lines of 32 bytes per instruction)
+      if constexpr (PW && !LINE) {
       if (piped && !gstat) {
         typedef cs_u32x4 u32x4;
         constexpr int NG = 4 * WNB;                            // column groups (of 8 columns) of the wave
@@ -1159,8 +1381,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         cs_pair_flag(p, opair, oamax);
         return;
       }
+      }
       // Every other epilogue of a TR kernel (GroupNorm partials, scale / shift, the scalar form, a tile across two row-vector
-      // samples, K slices): cold.  Each wave puts its 32x32 blocks back into the untransposed register layout through the
+      // samples, K slices of a pointwise launch, a three-tap launch with epilogue terms): cold. Each wave puts its 32x32 blocks back into the untransposed register layout through the
       // ring's LDS -- written by (row, column), read back by (column, row), 33-float rows -- and the code below runs as it
       // does on the other kernels, on the same values.
       {
