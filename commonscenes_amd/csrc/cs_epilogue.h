@@ -2,12 +2,15 @@
 // the epilogue terms, the interleaved fp16 operand pair of the result, and the fp64 column sums for the GroupNorm that
 // follows.  ONE source, so every site runs the same arithmetic in the same order and gives the same bits -- the split-K
 // reduce in its fused and two-kernel forms, the K-wave kernel and its one-chain twin, the Winograd output transform, the
-// float4 and scalar epilogues of the tile kernels.  Device code only, no state.  (One written-out copy remains: the pair
-// conversion and the 16-row column sum inside fused_splitk_reduce, cs_gemm_f16x3.hip, which says why.)
+// float4 and scalar epilogues of the tile kernels, the register-direct epilogues of the transposed-accumulator (TR) kernels
+// (cs_gemm_f16x3.hip: stores by row per lane or -- after cs_quad_transpose4 -- by whole lines).  Device code only,
+// no state.  (One written-out copy remains: the pair conversion and the 16-row column sum inside fused_splitk_reduce,
+// cs_gemm_f16x3.hip, which says why.)
 #pragma once
 #include "cs_common.h"
 
 typedef unsigned cs_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned cs_u32x2 __attribute__((ext_vector_type(2)));
 
 // ---- 1. the terms:  v += bias;  v = v * scale + shift;  v += rowvec[m / rv_rows];  v = act(v);  v += res  ----
 // D = CsConvGemm or CsFuseK (fields bias, scale, shift, rowvec, res, ldr, ldrv, rv_rows, act); one float4 at row m, column n.
@@ -49,9 +52,9 @@ __device__ __forceinline__ f32x4 cs_geglu4(f32x4 x, const f32x4& g) {
 // and the call sits in a branch that is uniform over the wave: every lane takes part in the half swap (quad_perm 1,0,3,2),
 // masked lanes with v = 0.  The even lane then holds [hi 8g .. 8g+7], the odd one [lo 8g .. 8g+7]: one 16-byte store each,
 // at byte cs_pair_off(first column of the lane) of the row.  `oamax` is the lane's running max |v * out_scale|.
-__device__ __forceinline__ cs_u32x4 cs_pair16(const f32x4& v, float out_scale, bool odd, float& oamax) {
+// (the conversion both forms share: o = v * out_scale -> running max |o|, H = the four hi halves, L = the four lo halves)
+__device__ __forceinline__ void cs_pair_split4(const f32x4& v, float out_scale, float& oamax, cs_u32x2& H, cs_u32x2& L) {
   typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   h4 hi, lo;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -60,7 +63,13 @@ __device__ __forceinline__ cs_u32x4 cs_pair16(const f32x4& v, float out_scale, b
     hi[e] = (_Float16)o;
     lo[e] = (_Float16)(o - (float)hi[e]);
   }
-  const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
+  H = __builtin_bit_cast(cs_u32x2, hi);
+  L = __builtin_bit_cast(cs_u32x2, lo);
+}
+__device__ __forceinline__ cs_u32x4 cs_pair16(const f32x4& v, float out_scale, bool odd, float& oamax) {
+  typedef cs_u32x2 u32x2;
+  u32x2 H, L;
+  cs_pair_split4(v, out_scale, oamax, H, L);
   const u32x2 send = odd ? H : L;
   u32x2 recv;
   recv[0] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)send[0], 0xB1, 0xF, 0xF, true);
@@ -77,19 +86,9 @@ __device__ __forceinline__ cs_u32x4 cs_pair16(const f32x4& v, float out_scale, b
 // row, the whole wave is active (v_permlane32_swap ignores EXEC for what it reads; a masked lane passes v = 0).  The swap
 // exchanges the upper half of the hi words with the lower half of the lo words, so lane l ends with [hi 8g .. 8g+7] and lane
 // l + 32 with [lo 8g .. 8g+7]: one 16-byte store each at byte cs_pair_off(first column of the lane) of the row, as above.
-// The conversion is cs_pair16's, expression for expression.
 __device__ __forceinline__ cs_u32x4 cs_pair16_half32(const f32x4& v, float out_scale, float& oamax) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  h4 hi, lo;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float o = v[e] * out_scale;
-    oamax = fmaxf(oamax, fabsf(o));
-    hi[e] = (_Float16)o;
-    lo[e] = (_Float16)(o - (float)hi[e]);
-  }
-  const u32x2 H = __builtin_bit_cast(u32x2, hi), L = __builtin_bit_cast(u32x2, lo);
+  cs_u32x2 H, L;
+  cs_pair_split4(v, out_scale, oamax, H, L);
   // (vdst = H, src = L: lanes 32-63 of H <-> lanes 0-31 of L)
   const auto s0 = __builtin_amdgcn_permlane32_swap(H[0], L[0], false, false);
   const auto s1 = __builtin_amdgcn_permlane32_swap(H[1], L[1], false, false);

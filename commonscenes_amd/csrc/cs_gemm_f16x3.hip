@@ -243,7 +243,8 @@ __device__ __forceinline__ void fused_splitk_reduce(const CsFuseK& f, const floa
   }
 }
 
-// f(integral_constant<int, I>) for I = 0 .. N-1, unrolled at compile time (the ring positions of the K loop)
+// f(integral_constant<int, I>) for I = 0 .. N-1, unrolled at compile time (the ring positions of the K loop, the taps of a
+// slab super-chunk, the passes of the pipelined epilogue)
 template <class F, int... I>
 __device__ __forceinline__ void static_steps(std::integer_sequence<int, I...>, F&& f) {
   (f(std::integral_constant<int, I>{}), ...);
@@ -608,12 +609,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
   // (pointwise only: a position GEMM's register-direct epilogue has no terms, and on the slab kernels that area holds the zero
   // block of the masked taps)
   constexpr int TRV = ROWBASE;                     // float [256] bias row, float [256] row-vector row
-  if constexpr (PW) {
-    static_assert(TRV + 2048 <= LDS_BYTES && BN <= 256 && (BN + 63) / 64 <= NW, "bias / row-vector rows beyond the ring");
-    if (wave < (BN + 63) / 64) {                   // 4 bytes per lane; columns past cout read zero
+  constexpr int BNV = (BN + 63) / 64;              // waves that fetch those rows
+  // LDS-DMA of the tile's bias row to tv[0 .. BN) and of its first sample's row-vector row to tv[256 .. 256 + BN): 4 bytes per
+  // lane, columns past cout read zero (here, and by the pipelined epilogue into its own area)
+  auto dma_vec_rows = [&](float* tv) {
+    if (wave < BNV) {
       const unsigned col = (unsigned)(64 * wave + lane);
       const unsigned off = col < (unsigned)BN ? (unsigned)(n0 + (int)col) * 4u : OOB;
-      float* const tv = reinterpret_cast<float*>(smem + TRV);
       if (p.bias) {
         const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, (unsigned)p.cout * 4u, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, tv + 64 * wave, 4, off, 0, 0, 0);
@@ -624,6 +626,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, tv + 256 + 64 * wave, 4, off, 0, 0, 0);
       }
     }
+  };
+  if constexpr (PW) {
+    static_assert(TRV + 2048 <= LDS_BYTES && BN <= 256 && BNV <= NW, "bias / row-vector rows beyond the ring");
+    dma_vec_rows(reinterpret_cast<float*>(smem + TRV));
   }
 
   f32x16 acc[WMB][WNB];
@@ -900,7 +906,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         }
       }
       if (j == 0) {
-        if constexpr (t9 == 0) issue_slab(sc + 1);       // its buffer was last read while chunk k-2 was computed
+        if constexpr (t9 == 0) issue_slab(sc + 1);      // its buffer was last read while chunk k-2 was computed
         issue_dma(dtap, dcc, dstage);
         advance();
 #pragma unroll
@@ -931,26 +937,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         m9[i] = (vmask[i] >> (TPK * kdc)) & TMASK;
         m9n[i] = (vmask[i] >> (TPK * kdn)) & TMASK;
       }
-      if constexpr (TPK == 9) {
-        sstep(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 2>{}, std::integral_constant<int, 5>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 0>{}, std::integral_constant<int, 6>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 1>{}, std::integral_constant<int, 7>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{}, sc, m9, m9n);
-      } else if constexpr (TPK == 3) {
-        sstep(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, sc, m9, m9n);
-      } else {
-        sstep(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, sc, m9, m9n);
-        sstep(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, sc, m9, m9n);
-      }
+      static_steps(std::make_integer_sequence<int, TPK>{}, [&](auto t9_c) {
+        sstep(std::integral_constant<int, decltype(t9_c)::value % NSTAGE>{}, t9_c, sc, m9, m9n);
+      });
       kdc = kdn;
     }
   } else
@@ -1041,7 +1030,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
     constexpr int RSLAB = KU * 1024;                         // one residual slab per wave
     constexpr int RES0 = NW * EPB;
     constexpr int VEC0 = RES0 + NW * 2 * RSLAB;
-    constexpr int BNV = (BN + 63) / 64;                      // waves that fetch the bias / row-vector rows
     static_assert(VEC0 + 2048 <= LDS_BYTES && BN <= 256 && BNV <= NW, "pipelined epilogue must fit in the kernel's LDS");
     const int m_last = min(m0 + BM, M) - 1;
     const bool geglu = p.act == CS_ACT_GEGLU;
@@ -1063,6 +1051,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
     const bool gstat = p.gn_part != nullptr;                 // per-(tile, column) GroupNorm partial sums
     const bool opair = p.out_format == 2;                    // `out` as the interleaved operand pair of out * out_scale
     if ((gstat || opair) && !piped && tid == 0 && p.status) atomicOr(p.status, CS_STATUS_INTERNAL);
+    // per-tile descriptor windows of the output and the residual (what `piped` admits: 32-bit offsets inside the tile's rows,
+    // from its first row to the tensor's end, clipped; the tensors themselves may be larger than a descriptor spans)
+    struct EpiWindows {
+      __amdgpu_buffer_rsrc_t ors, rrs;
+    };
+    auto epi_windows = [&]() -> EpiWindows {
+      const long long o_skip = ob * p.ldo * 4, r_skip = (long long)m0 * p.ldr * 4;
+      const long long o_cols = geglu ? p.cout / 2 : p.cout;
+      const long long o_left = ((Mo - 1) * p.ldo + o_cols) * 4 - o_skip;
+      const long long r_left = has_res ? ((long long)(M - 1) * p.ldr + p.cout) * 4 - r_skip : 0;
+      return {__builtin_amdgcn_make_buffer_rsrc((void*)((char*)p.out + o_skip), 0,
+                                                o_left > 0x7FF00000LL ? 0x7FF00000u : (unsigned)o_left, 0x00020000),
+              __builtin_amdgcn_make_buffer_rsrc((void*)(has_res ? (const char*)p.res + r_skip : (const char*)p.out), 0,
+                                                r_left > 0x7FF00000LL ? 0x7FF00000u : (r_left > 0 ? (unsigned)r_left : 0u),
+                                                0x00020000)};
+    };
     if constexpr (TR) {
       // ---- register-direct epilogue (TR kernels; what the pipelined path below serves, minus GroupNorm partials) ----
       // acc[i][j][4 g + e] is output row wm0 + 32 i + l31, column wn0 + 8 t + 4 half + e of the wave, t = 4 j + g: a float4
@@ -1114,15 +1118,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         typedef cs_u32x4 u32x4;
         constexpr int JB = (4 * WMB * WNB <= 16) ? WNB : 4 / WMB;      // blocks per residual batch: at most 16 float4s in flight
         static_assert(JB >= 1 && 4 * WMB * JB <= 16, "residual batches");
-        const long long o_skip = (long long)m0 * p.ldo * 4, r_skip = (long long)m0 * p.ldr * 4;
-        const long long o_cols = geglu ? p.cout / 2 : p.cout;
-        const long long o_left = ((long long)(M - 1) * p.ldo + o_cols) * 4 - o_skip;
-        const long long r_left = has_res ? ((long long)(M - 1) * p.ldr + p.cout) * 4 - r_skip : 0;
-        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((char*)p.out + o_skip), 0, o_left > 0x7FF00000LL ? 0x7FF00000u : (unsigned)o_left, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(has_res ? (const char*)p.res + r_skip : (const char*)p.out), 0,
-            r_left > 0x7FF00000LL ? 0x7FF00000u : (r_left > 0 ? (unsigned)r_left : 0u), 0x00020000);
+        const EpiWindows w = epi_windows();
+        const __amdgpu_buffer_rsrc_t ors = w.ors, rrs = w.rrs;
         // bias / row vector: added BEFORE the transposition, where a lane's column is that of its half-wave
         const float* const tvb = reinterpret_cast<const float*>(smem + TRV) + wn0 + 4 * half;
         const float* const tvr = tvb + 256;
@@ -1269,15 +1266,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
         constexpr int NG = 4 * WNB;                            // column groups (of 8 columns) of the wave
         constexpr int GB = (WMB * NG <= 16) ? NG : NG / 2;     // groups per residual batch: at most 16 float4s in flight
         static_assert(NG % GB == 0 && WMB * GB <= 16, "residual batches");
-        const long long o_skip = (long long)m0 * p.ldo * 4, r_skip = (long long)m0 * p.ldr * 4;
-        const long long o_cols = geglu ? p.cout / 2 : p.cout;
-        const long long o_left = ((long long)(M - 1) * p.ldo + o_cols) * 4 - o_skip;
-        const long long r_left = has_res ? ((long long)(M - 1) * p.ldr + p.cout) * 4 - r_skip : 0;
-        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)((char*)p.out + o_skip), 0, o_left > 0x7FF00000LL ? 0x7FF00000u : (unsigned)o_left, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(has_res ? (const char*)p.res + r_skip : (const char*)p.out), 0,
-            r_left > 0x7FF00000LL ? 0x7FF00000u : (r_left > 0 ? (unsigned)r_left : 0u), 0x00020000);
+        const EpiWindows w = epi_windows();
+        const __amdgpu_buffer_rsrc_t ors = w.ors, rrs = w.rrs;
         const float* const tvb = reinterpret_cast<const float*>(smem + TRV) + wn0 + 4 * half;
         const float* const tvr = tvb + 256;
         const int cl = n0 + wn0 + 4 * half;                    // the lane's column of group 0
@@ -1425,31 +1415,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
       float* const rs = reinterpret_cast<float*>(smem + RES0 + wave * 2 * RSLAB);
       float* const vb = reinterpret_cast<float*>(smem + VEC0);
       float* const vr = vb + 256;
-      // per-tile descriptor windows (32-bit offsets inside BM rows)
-      const long long o_skip = ob * p.ldo * 4, r_skip = (long long)m0 * p.ldr * 4;
-      const long long o_left = ((Mo - 1) * p.ldo + p.cout) * 4 - o_skip;
-      const long long r_left = has_res ? ((long long)(M - 1) * p.ldr + p.cout) * 4 - r_skip : 0;
-      const long long o_cols = geglu ? p.cout / 2 : p.cout;
-      const long long o_left2 = ((Mo - 1) * p.ldo + o_cols) * 4 - o_skip;
-      (void)o_left;
-      const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)((char*)p.out + o_skip), 0, o_left2 > 0x7FF00000LL ? 0x7FF00000u : (unsigned)o_left2, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(has_res ? (const char*)p.res + r_skip : (const char*)p.out), 0,
-          r_left > 0x7FF00000LL ? 0x7FF00000u : (r_left > 0 ? (unsigned)r_left : 0u), 0x00020000);
-      if (wave < BNV) {                                      // bias / row-vector rows: 4 bytes per lane
-        const unsigned col = (unsigned)(64 * wave + lane);
-        const unsigned off = col < (unsigned)BN ? (unsigned)(n0 + (int)col) * 4u : OOB;
-        if (p.bias) {
-          const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, (unsigned)p.cout * 4u, 0x00020000);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, vb + 64 * wave, 4, off, 0, 0, 0);
-        }
-        if (p.rowvec) {
-          const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(
-              (void*)(p.rowvec + (int64_t)(m0 / p.rv_rows) * p.ldrv), 0, (unsigned)p.cout * 4u, 0x00020000);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, vr + 64 * wave, 4, off, 0, 0, 0);
-        }
-      }
+      const EpiWindows w = epi_windows();
+      const __amdgpu_buffer_rsrc_t ors = w.ors, rrs = w.rrs;
+      dma_vec_rows(vb);
       auto pass_row = [&](int i, int q, int lrow) {
         return wm0 + 32 * i + 2 * (q & 1) + 8 * (q >> 1) + (lrow & 1) + 4 * (lrow >> 1);
       };
@@ -1472,8 +1440,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
       }
       __syncthreads();                                       // ... for every wave
       constexpr int NPASS = WMB * NQ;
-      auto do_pass = [&](auto i_c, auto q_c) {
-        constexpr int i = decltype(i_c)::value, q = decltype(q_c)::value, pass = i * NQ + q;
+      auto do_pass = [&](auto pass_c) {
+        constexpr int pass = decltype(pass_c)::value, i = pass / NQ, q = pass % NQ;
         if (has_res) {
           if constexpr (pass + 1 < NPASS) fetch_res(pass + 1);
           // younger than this pass's residual fetch: the previous pass's KU stores and the KU fetches just issued
@@ -1552,19 +1520,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 2) void conv_gemm_f16x3_ker
           }
         }
       };
-      auto all_q = [&](auto i_c) {
-        do_pass(i_c, std::integral_constant<int, 0>{});
-        do_pass(i_c, std::integral_constant<int, 1>{});
-        do_pass(i_c, std::integral_constant<int, 2>{});
-        do_pass(i_c, std::integral_constant<int, 3>{});
-        do_pass(i_c, std::integral_constant<int, 4>{});
-        do_pass(i_c, std::integral_constant<int, 5>{});
-        do_pass(i_c, std::integral_constant<int, 6>{});
-        do_pass(i_c, std::integral_constant<int, 7>{});
-      };
-      all_q(std::integral_constant<int, 0>{});
-      if constexpr (WMB > 1) all_q(std::integral_constant<int, 1>{});
-      static_assert(WMB <= 2 && NQ == 8, "pass enumeration");
+      static_steps(std::make_integer_sequence<int, NPASS>{}, do_pass);
       cs_pair_flag(p, opair, oamax);
       if (gstat) {
         // lanes -> [wave][staged row][column] in LDS, then thread t < BN adds column t over the waves that own it and
