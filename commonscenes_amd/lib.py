@@ -244,6 +244,10 @@ SIGNATURES = {
     "cs_clip_attn_causal": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _s]),
     "cs_clip_pool_eot": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _s]),
     "cs_feature_pair_l2": (_i, [_f, _f, _f, _i, _i, _i, _i, _f, _s]),
+    "cs_fid_moments": (_i, [_f, _i, _i, _i, _f, _f, _s]),
+    "cs_fid_widen": (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _s]),
+    "cs_fid_gram": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _s]),
+    "cs_fid_subset_sums": (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _i, _f, _f, _s]),
     "cs_abi_version": (_i, []),
 }
 

@@ -1186,6 +1186,41 @@ int cs_clip_pool_eot(const float* x, const int32_t* ids, float* out, int nb, int
 int cs_feature_pair_l2(const float* f, const int32_t* pairs, float* out, int n, int e, int npairs, int ld, int32_t* err,
                        cs_stream_t stream);
 
+/*
+ * FID / KID statistics in fp64 (csrc/cs_fid.hip; scripts/compute_fid_scores_3dfront.py -> cleanfid's frechet_distance and
+ * kernel_distance, restated from their published formulas).  Additions to ABI 18; every entry checks its arguments before any
+ * HIP call, only launches on `stream`, never synchronises, and uses no floating-point atomic: a result is a pure function of
+ * the inputs (fixed partition, fixed reduction order).
+ *
+ * cs_fid_moments: x fp32 [n][ldx] (d columns) -> mu fp64 [d], mu[c] = (sum_i x[i][c]) / n, and ss[0] = sum_i |x_i - mu|^2,
+ *   taken in a SECOND pass over the centred values (never as sum x^2 - n mu^2).  ss is fp64 [1 + CS_FID_MOMENT_CHUNKS(d)]:
+ *   ss[1 + j] holds the partial of columns [64 j, 64 j + 64), ss[0] their sum in index order.  Two launches.
+ * cs_fid_widen: out = (double)x - mu (mu fp64 [d]; NULL: a plain conversion), written as [n][ldo], or with transpose != 0 as
+ *   [d][ldo] (ldo >= n): the K-contiguous operand of the covariance product.  Loads and stores are coalesced in both
+ *   orientations (32 x 32 LDS tile).  Exactly one subtraction per element.
+ * cs_fid_gram: a fp64 [n1][lda], b fp64 [n2][ldb], both K-contiguous (k columns) -> g fp64 [n1][ldg],
+ *   g[i][j] = post(sum_k a[i][k] b[j][k]) on v_mfma_f64_16x16x4_f64.  mode 0: post = identity.  mode 1: p = s * gamma + coef0
+ *   (the product and the sum rounded separately), post = (p * p) * p -- the polynomial kernel of KID.  Any n1, n2, k >= 1, any
+ *   base alignment of 8: rows / columns past the matrices and the K tail are zero-filled, nothing is read past column k of a
+ *   row or past the last row, nothing is written past column n2 of a row.  The K order of one output element is the same in
+ *   every tile position: a sub-block computed alone carries the bits of that block inside the full matrix.  a may equal b.
+ * cs_fid_subset_sums: out[s] = sum over positions (p, q), p != q when skip_diag != 0, of kmat[ri[s][p]][ci[s][q]];
+ *   kmat fp64 [n_r][ldk] (n_c columns), ri / ci int32 [nsub][m] on the device, out fp64 [nsub].  One workgroup per subset:
+ *   wave w of 16 takes p = w, w + 16, ..., lane l takes q = l, l + 64, ...; lanes fold in a butterfly, waves in index order.
+ *   Every index is compared with n_r / n_c before anything is read through it: a bad one contributes NaN to its subset and sets
+ *   bit 0 of the sticky device word *err_word (as cs_cloud_resample does).
+ * CS_EINVAL for NULL pointers, sizes < 1, a leading dimension below its width, a mode other than 0 / 1.
+ */
+#define CS_FID_MOMENT_COLS 64
+#define CS_FID_MOMENT_CHUNKS(d) (((d) + CS_FID_MOMENT_COLS - 1) / CS_FID_MOMENT_COLS)
+int cs_fid_moments(const float* x, int n, int d, int ldx, double* mu, double* ss, cs_stream_t stream);
+int cs_fid_widen(const float* x, int n, int d, int ldx, const double* mu, double* out, int ldo, int transpose,
+                 cs_stream_t stream);
+int cs_fid_gram(const double* a, const double* b, double* g, int n1, int n2, int k, int lda, int ldb, int ldg, int mode,
+                double gamma, double coef0, cs_stream_t stream);
+int cs_fid_subset_sums(const double* kmat, int n_r, int n_c, int ldk, const int32_t* ri, const int32_t* ci, int nsub, int m,
+                       int skip_diag, double* out, int32_t* err_word, cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 
