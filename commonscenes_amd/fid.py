@@ -4,8 +4,10 @@ model_name="clip_vit_b_32")` and `compute_kid`) behind cleanfid's names, with th
 
     frechet_distance(feats1, feats2)   |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2), S the unbiased covariances (np.cov)
     kernel_distance(feats1, feats2)    cleanfid's KID: `num_subsets` random subsets of m rows, polynomial kernel (u.v / d + 1)^3
-    image_features(images, model)      clip.preprocess + CLIP.encode_image, as encode_image returns them (no L2 normalisation)
-    compute_fid / compute_kid          directories of .png (with a clip.CLIP) or ready features (tensors, arrays, .npy paths)
+    image_features(images, model)      clip.preprocess + CLIP.encode_image, as encode_image returns them (no L2 normalisation),
+                                       or inception.InceptionV3.encode_image (pool3, 2048 columns; mode= clean | legacy_pytorch)
+    compute_fid / compute_kid          directories of .png (with a clip.CLIP or an inception.InceptionV3) or ready features
+                                       (tensors, arrays, .npy paths)
     select_room(names, room)           the script's file filter
 
 tr sqrt(S1 S2) takes one of two routes.  "gram" (min(N1, N2) <= d): with A, B the centred feature matrices,
@@ -21,12 +23,14 @@ before the call selects the subsets cleanfid selects.
 
 Import swap for the script:
     from cleanfid import fid            ->  from commonscenes_amd import fid
+    fid.compute_fid(real, fake)                                            ->  fid.compute_fid(real, fake, model=inception_model)
     fid.compute_fid(real, fake, mode="clean", model_name="clip_vit_b_32")  ->  fid.compute_fid(real, fake, model=clip_model)
-    fid.compute_kid(real, fake)                                            ->  fid.compute_kid(real, fake, model=clip_model)
+    fid.compute_kid(real, fake)                                            ->  fid.compute_kid(real, fake, model=inception_model)
 
 cleanfid is not part of the build image: its definitions are restated here from its published formulas and parity with it is
 NOT pinned; whether its CLIP mode normalises the features could not be checked.  The InceptionV3 network (cleanfid's default
-feature extractor) and its image-resize modes are out of scope: pool3 features computed elsewhere enter as tensors / .npy.
+feature extractor) is commonscenes_amd/inception.py with the resize modes "clean" and "legacy_pytorch" ("legacy_tensorflow" is
+out of scope); pool3 features computed elsewhere still enter as tensors / .npy.
 """
 from __future__ import annotations
 
@@ -306,13 +310,19 @@ def kernel_distance(feats1: Tensor, feats2: Tensor, num_subsets: int = 100, max_
 # images -> features -> numbers
 # ----------------------------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def image_features(images, model, batch: int = 64) -> Tensor:
+def image_features(images, model, batch: int = 64, mode: Optional[str] = None) -> Tensor:
     """paths / PIL images (through clip.preprocess) or uint8 [B, S, S, 3] -> CLIP.encode_image features fp32 [N, E] on the
-    device, `batch` images per call, exactly as encode_image returns them."""
+    device, `batch` images per call, exactly as encode_image returns them.  With an inception.InceptionV3: its encode_image
+    (paths / PIL images or uint8 [B, H, W, 3]; `mode` = "clean", the default, or "legacy_pytorch") -> pool3 features [N, 2048]."""
     from . import clip as K
-    if not isinstance(model, K.CLIP) or model.vision is None:
+    from . import inception as I
+    incep = isinstance(model, I.InceptionV3)
+    if not incep and (not isinstance(model, K.CLIP) or model.vision is None):
         raise L.CsError("image_features: model must be a clip.CLIP with a vision tower")
-    size, batch = model.vision.resolution, max(1, int(batch))
+    if mode is not None and not incep:
+        raise L.CsError("image_features: mode= selects an InceptionV3 resize; a clip.CLIP has one preprocess")
+    batch = max(1, int(batch))
+    size = None if incep else model.vision.resolution
     tensor_in = isinstance(images, (torch.Tensor, np.ndarray))
     if not tensor_in:
         from PIL import Image
@@ -324,7 +334,10 @@ def image_features(images, model, batch: int = 64) -> Tensor:
     out = []
     for i in range(0, n, batch):
         chunk = images[i:i + batch]
-        out.append(model.encode_image(torch.as_tensor(chunk) if tensor_in else K.preprocess(chunk, size)))
+        if incep:
+            out.append(model.encode_image(torch.as_tensor(chunk) if tensor_in else chunk, mode=mode or "clean"))
+        else:
+            out.append(model.encode_image(torch.as_tensor(chunk) if tensor_in else K.preprocess(chunk, size)))
     return torch.cat(out) if len(out) > 1 else out[0]
 
 
@@ -334,7 +347,7 @@ def list_images(directory, room: str = "all") -> List[str]:
     return [os.path.join(str(directory), oi) for oi in select_room(sorted(os.listdir(str(directory))), room)]
 
 
-def features_of(src, model, room: str, batch: int, what: str) -> Tensor:
+def features_of(src, model, room: str, batch: int, what: str, mode: Optional[str] = None) -> Tensor:
     if isinstance(src, torch.Tensor):
         return src
     if isinstance(src, np.ndarray):
@@ -347,7 +360,7 @@ def features_of(src, model, room: str, batch: int, what: str) -> Tensor:
             files = list_images(path, room)
             if len(files) < 2:
                 raise ValueError(f"{what}: {len(files)} images of room {room!r} in {path}: a covariance needs two")
-            return image_features(files, model, batch)
+            return image_features(files, model, batch, mode=mode)
         arr = np.load(path)
     else:
         raise L.CsError(f"{what}: expected a directory, a .npy path, an array or a device tensor, got {type(src).__name__}")
@@ -357,18 +370,19 @@ def features_of(src, model, room: str, batch: int, what: str) -> Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
 
 
-def compute_fid(real, fake, model=None, room: str = "all", batch: int = 64, route: Optional[str] = None) -> float:
-    """cleanfid's compute_fid(fdir1, fdir2): `real` / `fake` are directories of .png (then `model` is a clip.CLIP and `room`
-    the script's filter) or features: fp32 device tensors, float32 arrays or .npy paths (how InceptionV3 pool3 features
-    computed elsewhere enter)."""
-    f1 = features_of(real, model, room, batch, "compute_fid")
-    f2 = features_of(fake, model, room, batch, "compute_fid")
+def compute_fid(real, fake, model=None, room: str = "all", batch: int = 64, route: Optional[str] = None,
+                mode: Optional[str] = None) -> float:
+    """cleanfid's compute_fid(fdir1, fdir2): `real` / `fake` are directories of .png (then `model` is a clip.CLIP or an
+    inception.InceptionV3 -- with `mode` its resize, "clean" by default -- and `room` the script's filter) or features: fp32
+    device tensors, float32 arrays or .npy paths (how features computed elsewhere enter)."""
+    f1 = features_of(real, model, room, batch, "compute_fid", mode)
+    f2 = features_of(fake, model, room, batch, "compute_fid", mode)
     return frechet_distance(f1, f2, route=route)
 
 
 def compute_kid(real, fake, model=None, room: str = "all", batch: int = 64, num_subsets: int = 100,
-                max_subset_size: int = 1000, seed: Optional[int] = None) -> float:
+                max_subset_size: int = 1000, seed: Optional[int] = None, mode: Optional[str] = None) -> float:
     """cleanfid's compute_kid(fdir1, fdir2) over the same inputs as compute_fid."""
-    f1 = features_of(real, model, room, batch, "compute_kid")
-    f2 = features_of(fake, model, room, batch, "compute_kid")
+    f1 = features_of(real, model, room, batch, "compute_kid", mode)
+    f2 = features_of(fake, model, room, batch, "compute_kid", mode)
     return kernel_distance(f1, f2, num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed)

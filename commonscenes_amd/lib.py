@@ -248,6 +248,10 @@ SIGNATURES = {
     "cs_fid_widen": (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _s]),
     "cs_fid_gram": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _s]),
     "cs_fid_subset_sums": (_i, [_f, _i, _i, _i, _f, _f, _i, _i, _i, _f, _f, _s]),
+    "cs_incep_input": (_i, [_f, _i, _i, _i, _i, _i, _i, _f, _i, _s]),
+    "cs_pool2d_max3": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
+    "cs_pool2d_avg3": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _s]),
+    "cs_pool2d_global_avg": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
     "cs_abi_version": (_i, []),
 }
 

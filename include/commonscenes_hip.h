@@ -1221,6 +1221,40 @@ int cs_fid_gram(const double* a, const double* b, double* g, int n1, int n2, int
 int cs_fid_subset_sums(const double* kmat, int n_r, int n_c, int ldk, const int32_t* ri, const int32_t* ci, int nsub, int m,
                        int skip_diag, double* out, int32_t* err_word, cs_stream_t stream);
 
+/*
+ * InceptionV3 pool3 features for FID / KID (commonscenes_amd/inception.py; scripts/compute_fid_scores_3dfront.py:
+ * fid.compute_fid / fid.compute_kid with cleanfid's default extractor): the image front end and the pooling layers.  The
+ * convolutions are cs_conv_gemm with din = kd = 1.  All tensors are NHWC fp32, rows are pixels with a leading dimension per
+ * row (ldx / ldo, in floats), so an input or an output may be a channel slice of a wider buffer.  One pass over the input, no
+ * atomics; a sample's result does not depend on its place in the batch.  Where c, the leading dimensions and both pointers
+ * are multiples of 4 floats / 16 bytes the kernels move float4 along C, otherwise one float per lane: the same arithmetic in
+ * the same order on both paths.
+ * cs_incep_input: img -> out fp32 [nb][299][299][cpad] (dense), channels 3 .. cpad - 1 zero.  is_float = 0: img is uint8
+ *   [nb][h][w][3], any h, w >= 1; resize = 1 resamples to 299 x 299 as F.interpolate(mode="bilinear", align_corners=False)
+ *   does, in fp32 on the 0..255 values: per axis src = (dst + 0.5) * in / out - 0.5 clamped below at 0, i0 = floor(src),
+ *   i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1, value = l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w *
+ *   v11); no antialiasing.  resize = 0 needs h = w = 299.  is_float = 1: img is float32 [nb][299][299][3] holding 0..255
+ *   values already resized on the host (resize must be 0).  norm 0: 2 * (v / 255) - 1 (pytorch-fid, cleanfid's
+ *   "legacy_pytorch"); norm 1: (v - 128) / 128 (cleanfid's "clean" wrapper).  Both constants are restated from those packages'
+ *   published sources; neither package is part of the build image.
+ * cs_pool2d_max3: 3 x 3 max pool, stride 1 or 2, pad 0 or 1; padded positions do not take part; output extent
+ *   (v + 2 * pad - 3) / stride + 1 per axis.  x [nb][h][w][ldx] -> out [nb][ho][wo][ldo].
+ * cs_pool2d_avg3: 3 x 3 average, stride 1, pad 1 (output extent = input extent).  count_include_pad = 0 divides by the
+ *   number of in-image taps (4 / 6 / 9), 1 by 9.  The in-image taps are summed in (kh, kw) order, then one division.
+ * cs_pool2d_global_avg: x [nb][h][w][ldx] -> out [nb][ldo] (c columns written): the mean over the h * w pixels, accumulated
+ *   in fp64 in pixel order and rounded once.
+ * CS_EINVAL, before any launch, for NULL pointers, pointers off their element alignment, extents < 1, ld < c, a stride / pad /
+ * flag outside the listed values, an output extent < 1, cpad < 3, and input or output row counts beyond int32.
+ */
+#define CS_INCEP_SIZE 299
+int cs_incep_input(const void* img, int is_float, int nb, int h, int w, int resize, int norm, float* out, int cpad,
+                   cs_stream_t stream);
+int cs_pool2d_max3(const float* x, float* out, int nb, int h, int w, int c, int ldx, int ldo, int stride, int pad,
+                   cs_stream_t stream);
+int cs_pool2d_avg3(const float* x, float* out, int nb, int h, int w, int c, int ldx, int ldo, int count_include_pad,
+                   cs_stream_t stream);
+int cs_pool2d_global_avg(const float* x, float* out, int nb, int h, int w, int c, int ldx, int ldo, cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

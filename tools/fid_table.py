@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """The FID / KID table of scripts/compute_fid_scores_3dfront.py through commonscenes_amd.fid.
 
-    python tools/fid_table.py --real DIR --fake DIR --clip {MODEL.pt | synthetic} [--room bedroom|livingroom|diningroom|all]
+    python tools/fid_table.py --real DIR --fake DIR [--clip {MODEL.pt | synthetic}]
+        [--inception {MODEL.pth | synthetic} [--inception-mode clean|legacy_pytorch]] [--room bedroom|livingroom|diningroom|all]
     python tools/fid_table.py --features REAL.npy FAKE.npy
     python tools/fid_table.py --synthetic N1 N2 D
         [--kid-subsets 100] [--kid-subset-size 1000] [--seed S] [--batch 64] [--compare-host]
@@ -9,6 +10,9 @@
 prints one `FID_TABLE {...}` JSON line: fid, kid, n_real, n_fake, d, route, kid_subsets, kid_subset_size, seed.  The
 directories are what `tools/eval_walkthrough.py --export-scenes DIR` writes (256 x 256 top-down PNGs named <RoomType>-...png).
 `--clip synthetic` runs the ViT-B/32 vision tower on synthetic weights (the numbers mean nothing; the path is the real one).
+--inception adds (or, without --clip, gives alone) the InceptionV3 pool3 numbers -- the reference prints both -- as an
+`inception` block: fid, kid, n_real, n_fake, d, route, mode, images_per_second (both directories through decode, resize and
+the network, one timed pass; report only).  MODEL.pth holds a state dict in torchvision's Inception3 names.
 --features takes float32 [N, d] arrays computed elsewhere (e.g. InceptionV3 pool3).  --compare-host adds the same two numbers
 from the numpy float64 formulas on the same features, with both wall times (report only; the device times follow one untimed
 pass)."""
@@ -65,11 +69,32 @@ def host_kid(f1, f2, num_subsets, max_subset_size):
     return float(t / num_subsets / m)
 
 
-def main(argv=None):
+def inception_block(args, dev, kid_kw):
+    """the `inception` block of the FID_TABLE line: InceptionV3 pool3 features of both directories, then the same statistics"""
+    from commonscenes_amd import fid, inception as I
+    if args.inception == "synthetic":
+        model = I.InceptionV3(dev).load_state_dict(I.synth_inception_state_dict(7))
+    else:
+        model = I.load_checkpoint(args.inception, dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    g1 = fid.features_of(args.real, model, args.room, args.batch, "fid_table", args.inception_mode)
+    g2 = fid.features_of(args.fake, model, args.room, args.batch, "fid_table", args.inception_mode)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    n1, n2, d = int(g1.shape[0]), int(g2.shape[0]), int(g1.shape[1])
+    return dict(fid=fid.frechet_distance(g1, g2), kid=fid.kernel_distance(g1, g2, **kid_kw), n_real=n1, n_fake=n2, d=d,
+                route=fid.pick_route(n1, n2, d), mode=args.inception_mode, images_per_second=(n1 + n2) / dt)
+
+
+def parse_args(argv=None):
+    """the command line with every check that needs no device"""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--real")
     ap.add_argument("--fake")
     ap.add_argument("--clip", help="MODEL.pt (OpenAI's ViT-B-32.pt) or 'synthetic'")
+    ap.add_argument("--inception", help="MODEL.pth (a state dict in torchvision's Inception3 names) or 'synthetic'")
+    ap.add_argument("--inception-mode", default="clean", choices=["clean", "legacy_pytorch"])
     ap.add_argument("--room", default="all", choices=["bedroom", "livingroom", "diningroom", "all"])
     ap.add_argument("--features", nargs=2, metavar=("REAL.npy", "FAKE.npy"))
     ap.add_argument("--synthetic", nargs=3, type=int, metavar=("N1", "N2", "D"))
@@ -82,28 +107,45 @@ def main(argv=None):
     modes = [args.synthetic is not None, args.features is not None, args.real is not None or args.fake is not None]
     if sum(modes) != 1:
         ap.error("give exactly one of --synthetic, --features, --real/--fake")
+    images = args.real is not None or args.fake is not None
+    if args.inception and not images:
+        ap.error("--inception reads images: it goes with --real / --fake")
+    if images and not (args.real and args.fake and (args.clip or args.inception)):
+        ap.error("--real and --fake go together, with --clip and / or --inception")
+    if args.compare_host and images and not args.clip:
+        ap.error("--compare-host compares the top-level numbers: give --clip, --features or --synthetic")
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     from commonscenes_amd import clip as K, fid
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
+    kid_kw = dict(num_subsets=args.kid_subsets, max_subset_size=args.kid_subset_size, seed=args.seed)
+    f1 = f2 = incep = None
     if args.synthetic is not None:
         f1, f2 = (torch.from_numpy(f).to(dev) for f in synthetic_features(*args.synthetic))
     elif args.features is not None:
         f1, f2 = (fid.features_of(p, None, "all", args.batch, "fid_table") for p in args.features)
     else:
-        if not (args.real and args.fake and args.clip):
-            ap.error("--real, --fake and --clip go together")
-        if args.clip == "synthetic":
-            model = K.CLIP(dev).load_state_dict(K.synth_clip_state_dict({"vision": K.VIT_B_32["vision"]}, 7))
-        else:
-            model = K.load_checkpoint(args.clip, dev)
-        f1 = fid.features_of(args.real, model, args.room, args.batch, "fid_table")
-        f2 = fid.features_of(args.fake, model, args.room, args.batch, "fid_table")
-    n1, n2, d = int(f1.shape[0]), int(f2.shape[0]), int(f1.shape[1])
-    route = fid.pick_route(n1, n2, d)
-    kid_kw = dict(num_subsets=args.kid_subsets, max_subset_size=args.kid_subset_size, seed=args.seed)
-    rec = dict(fid=fid.frechet_distance(f1, f2), kid=fid.kernel_distance(f1, f2, **kid_kw), n_real=n1, n_fake=n2, d=d,
-               route=route, kid_subsets=args.kid_subsets, kid_subset_size=min(n1, n2, args.kid_subset_size), seed=args.seed)
+        if args.clip:
+            if args.clip == "synthetic":
+                model = K.CLIP(dev).load_state_dict(K.synth_clip_state_dict({"vision": K.VIT_B_32["vision"]}, 7))
+            else:
+                model = K.load_checkpoint(args.clip, dev)
+            f1 = fid.features_of(args.real, model, args.room, args.batch, "fid_table")
+            f2 = fid.features_of(args.fake, model, args.room, args.batch, "fid_table")
+        if args.inception:
+            incep = inception_block(args, dev, kid_kw)
+    rec = dict(kid_subsets=args.kid_subsets, seed=args.seed)
+    if f1 is not None:
+        n1, n2, d = int(f1.shape[0]), int(f2.shape[0]), int(f1.shape[1])
+        route = fid.pick_route(n1, n2, d)
+        rec = dict(fid=fid.frechet_distance(f1, f2), kid=fid.kernel_distance(f1, f2, **kid_kw), n_real=n1, n_fake=n2, d=d,
+                   route=route, kid_subsets=args.kid_subsets, kid_subset_size=min(n1, n2, args.kid_subset_size), seed=args.seed)
+    if incep is not None:
+        rec["inception"] = incep
     if args.compare_host:
         def timed(fn):
             torch.cuda.synchronize()
