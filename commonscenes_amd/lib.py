@@ -252,6 +252,11 @@ SIGNATURES = {
     "cs_pool2d_max3": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "cs_pool2d_avg3": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _i, _s]),
     "cs_pool2d_global_avg": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
+    "cs_mesh_sdf_plan": (_i, [_l, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "cs_mesh_sdf_moments": (_i, [_f, _l, _f, _l, _f, _i, _f, _f, _f, _s]),
+    "cs_mesh_sdf_pack": (_i, [_f, _l, _f, _l, _f, _i, _f, _f, _f, _s]),
+    "cs_mesh_sdf_grid": (_i, [_f, _l, _f, _i, _i, _fl, _i, _f, _l, _f, _s]),
+    "cs_mesh_sdf_finish": (_i, [_f, _l, _f, _i, _i, _i, _fl, _fl, _f, _f, _s]),
     "cs_abi_version": (_i, []),
 }
 
@@ -309,6 +314,9 @@ STATUS_F16X3_OVERFLOW = 1
 STATUS_INTERNAL = 2
 STATUS_SPLITK_TIMEOUT = 4
 STATUS_CONSTRAINT_RANGE = 8
+# cs_mesh_sdf_*: per-mesh status bits (CS_SDF_STATUS_*) and the sizes its hosts need
+SDF_STATUS_INDEX, SDF_STATUS_NONFINITE, SDF_STATUS_RANGE, SDF_STATUS_EMPTY = 1, 2, 4, 8
+SDF_CHUNK, SDF_MAX_SLICES, SDF_MOMENT_BLOCKS = 256, 64, 16
 
 
 def check(rc: int, what: str) -> None:

@@ -1255,6 +1255,57 @@ int cs_pool2d_avg3(const float* x, float* out, int nb, int h, int w, int c, int 
                    cs_stream_t stream);
 int cs_pool2d_global_avg(const float* x, float* out, int nb, int h, int w, int c, int ldx, int ldo, cs_stream_t stream);
 
+/*
+ * Mesh -> SDF grid (csrc/cs_sdf.hip; commonscenes_amd/mesh_sdf.py).  Stands in for the grids the reference READS from
+ * `ori_sample_grid.h5` (dataset/threedfront_dataset.py:387-392; model/diff_utils/util_3d.py:50-56), which an external
+ * preprocessing binary produced, after the unit-sphere normalisation of util_3d.py:481-512 (get_normalize_mesh).  Additions to
+ * ABI 18; every entry checks its arguments before any HIP call, only launches on `stream`, never synchronises, and uses no
+ * floating-point atomic: a mesh's grid is a pure function of that mesh, n and bound, whatever else is in the batch.
+ *
+ * A batch is packed and ragged: verts fp32 [total_verts][3], faces int64 [total_faces][3] with mesh-LOCAL vertex ids, and
+ * meta int64 [nb][6] on the device, row m = (vert_base, vert_count, face_base, face_count, slices, ws_offset in bytes).
+ * status is int32 [nb] on the device, zeroed by the caller, OR-ed into (CS_SDF_STATUS_*); a mesh whose meta row leaves a buffer
+ * is skipped whole.  Array index [i][j][k] of a grid is (x, y, z); node i of an axis sits at -bound + i * 2 bound / (n - 1).
+ *
+ * cs_mesh_sdf_plan: host only (no HIP call).  slices = how many runs of CS_SDF_CHUNK-triangle chunks the mesh's triangle range
+ *   is cut into across workgroups, a function of (face_count, n) ONLY; ws_bytes = the workspace of that mesh (a multiple of
+ *   16): per slice n^3 fp64 angle sums, then per slice n^3 fp32 squared distances.
+ * cs_mesh_sdf_moments: per mesh the exact area-weighted centroid of its triangles and the largest distance of a used vertex
+ *   from it, both in fp64 -- the limits of what get_normalize_mesh estimates from 16384 random surface samples.  partial is
+ *   fp64 [nb][CS_SDF_MOMENT_BLOCKS][4] scratch (per-block sums, folded in block order); norm fp64 [nb][4] = (cx, cy, cz,
+ *   scale).  A mesh without area or extent gets (0, 0, 0, 1) and CS_SDF_STATUS_EMPTY.  Two launches.
+ * cs_mesh_sdf_pack: tris fp32 [total_faces][12], 16-byte aligned: corners a, b, c after (v - centroid) / scale (fp64, rounded
+ *   once) in lexicographic order, and n = +-(b - a) x (c - a) with the face's orientation as its sign: a mesh with every face
+ *   reversed packs the same corners and the negated normals (same distances bit for bit, w negated).  Every face id is compared with vert_count before anything is read through it and every
+ *   used vertex is tested for finiteness: a bad one sets CS_SDF_STATUS_INDEX / _NONFINITE and writes a record that contributes
+ *   nothing (a far point, normal 0).  A triangle whose height is below sqrt(2^-23) of its longest edge is written as that edge
+ *   (a, b, b) with normal 0: distance to the segment, solid angle 0; a point triangle likewise.
+ * cs_mesh_sdf_grid: for every node the squared distance |p - q|^2 to the closest point q of any triangle (Ericson's region
+ *   walk) and the sum of atan2 terms of the Van Oosterom-Strackee solid angle, per slice, into ws at the mesh's ws_offset.
+ *   max_slices = the largest `slices` of the batch (grid y extent).  A meta row whose slices is not cs_mesh_sdf_plan's, or whose
+ *   workspace range leaves [0, ws_bytes), sets CS_SDF_STATUS_RANGE and writes nothing.
+ * cs_mesh_sdf_finish: out fp32 [nb][n][n][n]: slices merged in slice order (min; fp64 sum), w = sum Omega / 4 pi,
+ *   value = -d where use_sign != 0 and |w| >= wind_level, else +d; clamped to [-trunc, trunc] where trunc > 0.  wout (may be
+ *   NULL) receives w.
+ * CS_EINVAL for NULL pointers, nb < 1, n outside 2..1024, bound <= 0, a misaligned tris / ws.
+ */
+#define CS_SDF_CHUNK 256
+#define CS_SDF_MAX_SLICES 64
+#define CS_SDF_MOMENT_BLOCKS 16
+#define CS_SDF_STATUS_INDEX 1
+#define CS_SDF_STATUS_NONFINITE 2
+#define CS_SDF_STATUS_RANGE 4
+#define CS_SDF_STATUS_EMPTY 8
+int cs_mesh_sdf_plan(int64_t face_count, int n, int32_t* slices, int64_t* ws_bytes);
+int cs_mesh_sdf_moments(const float* verts, int64_t total_verts, const int64_t* faces, int64_t total_faces,
+                        const int64_t* meta, int nb, double* partial, double* norm, int32_t* status, cs_stream_t stream);
+int cs_mesh_sdf_pack(const float* verts, int64_t total_verts, const int64_t* faces, int64_t total_faces, const int64_t* meta,
+                     int nb, const double* norm, float* tris, int32_t* status, cs_stream_t stream);
+int cs_mesh_sdf_grid(const float* tris, int64_t total_faces, const int64_t* meta, int nb, int n, float bound, int max_slices,
+                     void* ws, int64_t ws_bytes, int32_t* status, cs_stream_t stream);
+int cs_mesh_sdf_finish(const void* ws, int64_t ws_bytes, const int64_t* meta, int nb, int n, int use_sign, float wind_level,
+                       float trunc, float* out, float* wout, cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

@@ -7,6 +7,8 @@
   * model.pth: the layout VAEGAN_V2FULL.py:687-699 writes ('df' + 'vqvae'; the VQ-VAE needs its encoder.* entries).
   * --sdf: a .npy of [N, 1, 64, 64, 64] (or [N, 64, 64, 64] / [64, 64, 64]) fp32 SDFs; --range: the KNOWN box in [-1, 1]^3
     (tensor axes 2, 3, 4 of the SDF take the x, y, z ranges, as diff_utils/demo_util.py:172-254 has it).
+  * --mesh FILE.obj in place of --sdf: the mesh is normalised into the unit sphere and sampled to a 64^3 SDF truncated at 0.2
+    on the device (commonscenes_amd/mesh_sdf.py; also with --synthetic weights).
   * --cond: [N, 1, 1280] conditions (the scene-graph embedding rel2shape would pass); a zero context otherwise.  The
     unconditional embedding is a zero context.
   * --obj DIR: the completed shapes as DIR/obj{n}_gen{k}.obj through sdf_to_mesh (marching cubes on the device).
@@ -74,6 +76,8 @@ def main():
     ap.add_argument("checkpoint", nargs="?", help="model{epoch}.pth in the reference's layout ('df' + 'vqvae')")
     ap.add_argument("--synthetic", action="store_true", help="synthetic weights and inputs instead of files")
     ap.add_argument("--sdf", help=".npy of [N,1,64,64,64] fp32 SDFs")
+    ap.add_argument("--mesh", help=".obj instead of --sdf: normalised into the unit sphere and sampled to a 64^3 SDF truncated at "
+                                   "0.2 (commonscenes_amd.mesh_sdf.mesh_to_sdf)")
     ap.add_argument("--range", type=float, nargs=6, metavar=("x0", "x1", "y0", "y1", "z0", "z1"),
                     help="the known box inside [-1, 1]^3")
     ap.add_argument("--cond", help=".npy of [N,1,1280] conditions (default: a zero context)")
@@ -86,8 +90,10 @@ def main():
     ap.add_argument("--step-rows", type=int, default=32, help="--synthetic: rows of the masked / unmasked step timing (0: skip)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X (no CPU path)"
-    if not a.synthetic and not (a.checkpoint and a.sdf and a.range):
-        ap.error("give model.pth --sdf FILE.npy --range x0 x1 y0 y1 z0 z1, or --synthetic")
+    if a.sdf and a.mesh:
+        ap.error("--sdf and --mesh are alternatives")
+    if not a.synthetic and not (a.checkpoint and (a.sdf or a.mesh) and a.range):
+        ap.error("give model.pth --sdf FILE.npy (or --mesh FILE.obj) --range x0 x1 y0 y1 z0 z1, or --synthetic")
     from commonscenes_amd import configs as K, synth
     from commonscenes_amd.sdfusion import SDFusionText2ShapeModel
     from commonscenes_amd.unet import unet_param_shapes
@@ -115,6 +121,11 @@ def main():
     if a.sdf:
         x = torch.from_numpy(np.asarray(np.load(a.sdf), np.float32)).reshape(-1, 1, 64, 64, 64)
         sdf_src = a.sdf
+    elif a.mesh:
+        from commonscenes_amd.mesh_sdf import mesh_to_sdf, read_obj
+        mv, mf = read_obj(a.mesh)
+        x = mesh_to_sdf([mv], [mf], res=64, trunc=0.2).cpu()
+        sdf_src = f"{a.mesh} ({mf.shape[0]} faces) through mesh_to_sdf"
     else:
         x = torch.cat([synth.sdf_volume(0), synth.sdf_volume(1)], dim=0)
         sdf_src = "synth.sdf_volume(0), (1)"

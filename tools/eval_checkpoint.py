@@ -11,6 +11,8 @@ logs, computed forward-only on held-out SDFs.
   * the VQ-VAE's reconstruction iou / iou_std at threshold 0 and its L1 (VQVAEModel.eval_metrics, vqvae_model.py:138-168).
 The checkpoint is the layout VAEGAN_V2FULL.py:687-699 writes ('df' + 'vqvae'; the VQ-VAE needs its encoder.* entries).
 --sdfs: a .npy of [N, 1, 64, 64, 64] (or [N, 64, 64, 64]) fp32 SDFs, or a .npz with `sdf` and optionally `cond` [N, 1, 1280].
+--meshes DIR in place of --sdfs: every DIR/*.obj, normalised into the unit sphere and sampled to a 64^3 SDF truncated at 0.2 on the
+device (commonscenes_amd/mesh_sdf.py).
 Prints a table and one JSON line (`EVAL_CHECKPOINT {...}`); shapes per second are for the record only.
 """
 import argparse
@@ -35,6 +37,8 @@ def main():
     ap.add_argument("checkpoint", nargs="?", help="model{epoch}.pth in the reference's layout ('df' + 'vqvae')")
     ap.add_argument("--synthetic", action="store_true", help="synthetic weights instead of a checkpoint file")
     ap.add_argument("--sdfs", help=".npy [N,1,64,64,64] or .npz with 'sdf' (and optionally 'cond')")
+    ap.add_argument("--meshes", help="directory of .obj files instead of --sdfs: each is normalised into the unit sphere and sampled "
+                                     "to a 64^3 SDF truncated at 0.2 (commonscenes_amd.mesh_sdf.mesh_to_sdf)")
     ap.add_argument("--timesteps", default="1,100,250,500,750,999")
     ap.add_argument("--width", type=int, default=224, help="UNet model_channels of the checkpoint (224 = the shipped config)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the device generator that draws the noise")
@@ -44,6 +48,8 @@ def main():
     assert torch.cuda.is_available(), "needs the MI355X (no CPU path)"
     if not a.synthetic and not a.checkpoint:
         ap.error("give a checkpoint file or --synthetic")
+    if a.sdfs and a.meshes:
+        ap.error("--sdfs and --meshes are alternatives")
     from commonscenes_amd import configs as K, synth
     from commonscenes_amd.sdfusion import SDFusionText2ShapeModel
     from commonscenes_amd.unet import unet_param_shapes
@@ -77,9 +83,20 @@ def main():
             cond = torch.from_numpy(np.asarray(blob["cond"], np.float32))
         x = torch.from_numpy(np.asarray(sdf, np.float32)).reshape(-1, 1, 64, 64, 64)
         sdf_src = a.sdfs
+    elif a.meshes:
+        from commonscenes_amd.mesh_sdf import mesh_to_sdf, read_obj
+        files = sorted(Path(a.meshes).glob("*.obj"))
+        if not files:
+            ap.error(f"no .obj file in {a.meshes}")
+        parts = []
+        for i in range(0, len(files), 8):
+            vf = [read_obj(f) for f in files[i:i + 8]]
+            parts.append(mesh_to_sdf([v for v, _ in vf], [f for _, f in vf], res=64, trunc=0.2).cpu())
+        x = torch.cat(parts, dim=0)
+        sdf_src = f"{len(files)} meshes of {a.meshes} through mesh_to_sdf"
     else:
         if not a.synthetic:
-            ap.error("--sdfs is required with a checkpoint file")
+            ap.error("--sdfs or --meshes is required with a checkpoint file")
         v0, v1 = synth.sdf_volume(0), synth.sdf_volume(1)
         x = torch.cat([v0, v1, v0.flip(2), v1.flip(3)], dim=0)
         sdf_src = "synth.sdf_volume variants"
