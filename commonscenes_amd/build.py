@@ -15,7 +15,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_NAME = "libcommonscenes_hip.so"
 LIB_PATH = PKG_DIR / LIB_NAME
-SOURCES = ["cs_plan.hip", "cs_gemm.hip", "cs_gemm_f16x3.hip", "cs_gemm_kw.hip", "cs_mesh.hip", "cs_scene.hip", "cs_view.hip", "cs_constraints.hip", "cs_metrics.hip", "cs_pairwise.hip", "cs_diversity.hip", "cs_norm.hip", "cs_twin_ln.hip", "cs_attention.hip", "cs_attention_f16x3.hip", "cs_ops.hip", "cs_unet.hip", "cs_vqvae.hip", "cs_vqenc.hip", "cs_eval.hip", "cs_complete.hip", "cs_clip.hip", "cs_fid.hip", "cs_incep.hip", "cs_sdf.hip"]
+SOURCES = ["cs_plan.hip", "cs_gemm.hip", "cs_gemm_f16x3.hip", "cs_gemm_kw.hip", "cs_mesh.hip", "cs_scene.hip", "cs_view.hip", "cs_constraints.hip", "cs_metrics.hip", "cs_pairwise.hip", "cs_diversity.hip", "cs_norm.hip", "cs_twin_ln.hip", "cs_attention.hip", "cs_attention_f16x3.hip", "cs_ops.hip", "cs_unet.hip", "cs_vqvae.hip", "cs_vqenc.hip", "cs_eval.hip", "cs_complete.hip", "cs_clip.hip", "cs_fid.hip", "cs_incep.hip", "cs_sdf.hip", "cs_scene_lib.hip"]
 HEADERS = [CSRC / "cs_common.h", CSRC / "cs_f16x3.h", CSRC / "cs_epilogue.h", CSRC / "cs_mc_tables.h", CSRC / "cs_driver.h", CSRC / "cs_vq.h", CSRC / "cs_ln_pair.h", CSRC / "cs_attention_core.h", CSRC / "cs_raster.h", PKG_DIR.parent / "include" / "commonscenes_hip.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}", "-Wall",

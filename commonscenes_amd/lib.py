@@ -257,6 +257,9 @@ SIGNATURES = {
     "cs_mesh_sdf_pack": (_i, [_f, _l, _f, _l, _f, _i, _f, _f, _f, _s]),
     "cs_mesh_sdf_grid": (_i, [_f, _l, _f, _i, _i, _fl, _i, _f, _l, _f, _s]),
     "cs_mesh_sdf_finish": (_i, [_f, _l, _f, _i, _i, _i, _fl, _fl, _f, _f, _s]),
+    "cs_scene_retrieve": (_i, [_f, _l, _f, _i, _f, _l, _f, _l, _f, _f, _f, _s]),
+    "cs_scene_place_boxes": (_i, [_f, _l, _i, _f, _f, _s]),
+    "cs_scene_box_markers": (_i, [_f, _l, _f, _f, _f, _f, _i, _fl, _f, _f, _l, _f, _f, _l, _s]),
     "cs_abi_version": (_i, []),
 }
 
@@ -317,6 +320,9 @@ STATUS_CONSTRAINT_RANGE = 8
 # cs_mesh_sdf_*: per-mesh status bits (CS_SDF_STATUS_*) and the sizes its hosts need
 SDF_STATUS_INDEX, SDF_STATUS_NONFINITE, SDF_STATUS_RANGE, SDF_STATUS_EMPTY = 1, 2, 4, 8
 SDF_CHUNK, SDF_MAX_SLICES, SDF_MOMENT_BLOCKS = 256, 64, 16
+# cs_scene_retrieve: per-query status bits (CS_RETRIEVE_STATUS_*); cs_scene_box_markers: the range of `sections`
+RETRIEVE_STATUS_NONFINITE, RETRIEVE_STATUS_CATEGORY, RETRIEVE_STATUS_EMPTY, RETRIEVE_STATUS_NODISTANCE = 1, 2, 4, 8
+MARKER_MIN_SECTIONS, MARKER_MAX_SECTIONS = 3, 64
 
 
 def check(rc: int, what: str) -> None:

@@ -9,7 +9,8 @@ writes the scene buffers in one pass and rasterises them (exact integer coverage
 
 The names mirror the reference's so that a script swaps the import.  What differs, on purpose:
   * meshes are `TriMesh` records of device tensors (vertices, faces, vertex_colors), not trimesh objects;
-  * `render_boxes=True` (tube markers, trimesh.creation.cylinder) is not built and raises;
+  * `render_boxes=True` draws this package's own tube markers (csrc/cs_scene_lib.hip: trimesh.creation.cylinder's vertex order
+    cannot be pinned without trimesh); `get_generated_models_v2` still raises on it, `assemble_scene` is the marker path;
   * export is plain-text OBJ with vertex colours (no glb);
   * the shading of `render_topdown` is this package's (base colour x (0.3 + 0.7 max(0, n_y))): pyrender's lights cannot be
     pinned without pyrender.  Coverage, depth and object ids follow the reference's camera exactly.
@@ -59,6 +60,7 @@ class SceneMesh:
     kept: List[int]
     vert_counts: List[int] = field(default_factory=list)
     face_counts: List[int] = field(default_factory=list)
+    sources: List[str] = field(default_factory=list)       # assemble_scene_from_library: model id / file per kept object
 
     def per_object(self) -> List[TriMesh]:
         out, v0, f0 = [], 0, 0
@@ -166,10 +168,13 @@ def _fit(vptr: int, vrows: int, vbase: Tensor, vcount: Tensor, box7: Tensor, deg
 
 
 def _assemble(verts_list, faces_list, node_of_mesh: List[int], box7: Tensor, keep_nodes: List[bool], colors: np.ndarray,
-              degrees: bool, flip: bool, extra_verts: int = 0, extra_faces: int = 0):
+              degrees: bool, flip: bool, extra_verts: int = 0, extra_faces: int = 0, placed: bool = False,
+              mark_nodes: Optional[List[bool]] = None, sections: int = 4, radius: float = 0.006):
     """fit + apply over N nodes; mesh k belongs to node node_of_mesh[k]; the other nodes own no vertices.
     -> (out_verts, out_rgb, out_faces, face_object, box_points, xform, kept nodes, vert counts, face counts); the outputs have
-    `extra_*` spare rows at the end (the floor)."""
+    `extra_*` spare rows at the end (the floor).  placed: retrieval's placement (cs_scene_place_boxes) instead of the fit.
+    mark_nodes: the nodes whose box gets tube markers, written after all objects, in input order (cs_scene_box_markers);
+    they are appended to kept / counts."""
     dev = box7.device
     n = box7.shape[0]
     vptr, vrows, vb, vc, vown = _ragged(verts_list, torch.float32, dev)
@@ -186,8 +191,10 @@ def _assemble(verts_list, faces_list, node_of_mesh: List[int], box7: Tensor, kee
     meta = _i64(nvb + nvc + nfb + nfc + ovb + ofb, dev).view(6, n)          # one small upload
     keep = torch.tensor(keep_nodes, dtype=torch.bool).to(dev)
     col = torch.from_numpy(np.ascontiguousarray(colors, dtype=np.float32)).to(dev)
-    xform, pts = _fit(vptr, vrows, meta[0], meta[1], box7, degrees)
-    tv, tf = v0 + extra_verts, f0 + extra_faces
+    xform, pts = _place(box7, degrees) if placed else _fit(vptr, vrows, meta[0], meta[1], box7, degrees)
+    marked = [j for j in range(n) if mark_nodes is not None and mark_nodes[j]]
+    mv, mf = 12 * (2 * sections + 2), 48 * sections
+    tv, tf = v0 + len(marked) * mv + extra_verts, f0 + len(marked) * mf + extra_faces
     out_v = torch.empty((max(tv, 1), 3), dtype=torch.float32, device=dev)     # (never a NULL pointer for an empty scene)
     out_c = torch.empty((max(tv, 1), 3), dtype=torch.float32, device=dev)
     out_f = torch.empty((max(tf, 1), 3), dtype=torch.int64, device=dev)
@@ -198,8 +205,42 @@ def _assemble(verts_list, faces_list, node_of_mesh: List[int], box7: Tensor, kee
                                     out_c.data_ptr(), v0, out_f.data_ptr(), out_o.data_ptr(), f0, _stream()),
             "cs_scene_apply")
     del vown, fown
-    return (out_v[:tv], out_c[:tv], out_f[:tf], out_o[:tf], pts, xform, kept, [nvc[j] for j in kept],
-            [nfc[j] for j in kept])
+    nv_kept, nf_kept = [nvc[j] for j in kept], [nfc[j] for j in kept]
+    if marked:
+        mvb, mfb = [0] * n, [0] * n
+        for k, j in enumerate(marked):
+            mvb[j], mfb[j] = v0 + k * mv, f0 + k * mf
+        mmeta = _i64(mvb + mfb, dev).view(2, n)
+        mkeep = torch.tensor([bool(mark_nodes[j]) for j in range(n)], dtype=torch.bool).to(dev)
+        L.check(L.load().cs_scene_box_markers(pts.data_ptr(), n, mkeep.data_ptr(), mmeta[0].data_ptr(), mmeta[1].data_ptr(),
+                                              col.data_ptr(), sections, float(radius), out_v.data_ptr(), out_c.data_ptr(),
+                                              v0 + len(marked) * mv, out_f.data_ptr(), out_o.data_ptr(), f0 + len(marked) * mf,
+                                              _stream()), "cs_scene_box_markers")
+        kept, nv_kept, nf_kept = kept + marked, nv_kept + [mv] * len(marked), nf_kept + [mf] * len(marked)
+    return out_v[:tv], out_c[:tv], out_f[:tf], out_o[:tf], pts, xform, kept, nv_kept, nf_kept
+
+
+def _place(box7: Tensor, degrees: bool) -> Tuple[Tensor, Tensor]:
+    n = box7.shape[0]
+    xform = torch.empty((n, 12), dtype=torch.float32, device=box7.device)
+    pts = torch.empty((n, 8, 3), dtype=torch.float32, device=box7.device)
+    L.check(L.load().cs_scene_place_boxes(box7.data_ptr(), n, int(bool(degrees)), xform.data_ptr(), pts.data_ptr(), _stream()),
+            "cs_scene_place_boxes")
+    return xform, pts
+
+
+def _check_marker(sections, radius) -> Tuple[int, float]:
+    if isinstance(sections, bool) or not isinstance(sections, (int, np.integer)) or \
+            not L.MARKER_MIN_SECTIONS <= int(sections) <= L.MARKER_MAX_SECTIONS:
+        raise L.CsError(f"scene_mesh: marker sections must be an integer in {L.MARKER_MIN_SECTIONS}..{L.MARKER_MAX_SECTIONS}, "
+                        f"got {sections!r}")
+    try:
+        r = float(np.float32(radius))                      # the kernel takes the fp32 value
+    except (TypeError, ValueError):
+        raise L.CsError(f"scene_mesh: marker radius must be a number, got {radius!r}") from None
+    if not (r > 0.0) or not np.isfinite(r):
+        raise L.CsError(f"scene_mesh: marker radius must be positive and finite, got {radius!r}")
+    return int(sections), r
 
 
 def _box7(box, dev) -> Tensor:
@@ -224,13 +265,18 @@ def fit_shapes_to_box_v2(verts: Tensor, faces: Tensor, box, degrees: bool = Fals
 
 def _plan(boxes, meshes: Meshes, cat_ids, classes, colors, without_lamp: bool):
     """the reference's loop (:307-328) as index lists: which node each mesh belongs to, which nodes are kept, colours"""
+    return _plan_nodes(boxes, len(meshes), cat_ids, classes, colors, without_lamp)
+
+
+def _plan_nodes(boxes, n_meshes: Optional[int], cat_ids, classes, colors, without_lamp: bool):
+    """`_plan` without the meshes (n_meshes None: the caller chooses them afterwards, one per shaped node)"""
     shape = tuple(torch.as_tensor(boxes).shape)
     cats = _check_inputs(shape[0] if shape else 0, shape, cat_ids, classes)
     labels = [_label(classes, c) for c in cats]
     shaped = [j for j, lab in enumerate(labels) if not _skipped(lab)]
-    if len(meshes) != len(shaped):
+    if n_meshes is not None and n_meshes != len(shaped):
         raise L.CsError(f"scene_mesh: {len(shaped)} shaped objects (boxes that are neither _scene_ nor floor) but "
-                        f"{len(meshes)} shapes")
+                        f"{n_meshes} shapes")
     if colors is None:
         colors = hls_palette(len(classes))[cats]
     colors = np.asarray(colors.detach().cpu() if isinstance(colors, torch.Tensor) else colors, dtype=np.float64)
@@ -300,34 +346,269 @@ def create_floor(box_and_angle, cat_ids, classes) -> TriMesh:
     return TriMesh(torch.from_numpy(v), torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int64))
 
 
+def _floor_rows(labels: List[str], what: str) -> List[int]:
+    rows = [j for j in range(len(labels)) if labels[j] != "_scene_"]
+    if not rows:
+        raise L.CsError(f"{what}: no box besides _scene_ to span the floor")
+    return rows
+
+
+def _add_floor(v, c, f, o, pts, rows: List[int], n: int):
+    """the floor quad into the last 4 vertex / 2 face rows, from the device box corners (create_floor's rows 0, 1, 4, 5)"""
+    bottom = pts[torch.tensor(rows, dtype=torch.int64).to(v.device)][:, [0, 1, 4, 5]]
+    x0, x1, z0, z1 = bottom[..., 0].min(), bottom[..., 0].max(), bottom[..., 2].min(), bottom[..., 2].max()
+    zero = torch.zeros((), dtype=torch.float32, device=v.device)
+    nv0, nf0 = v.shape[0] - 4, f.shape[0] - 2
+    v[nv0:] = torch.stack([torch.stack([x0, zero, z0]), torch.stack([x0, zero, z1]), torch.stack([x1, zero, z1]),
+                           torch.stack([x1, zero, z0])])
+    c[nv0:] = torch.tensor(FLOOR_RGB, dtype=torch.float32, device=v.device)
+    f[nf0:] = torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int64, device=v.device) + nv0
+    o[nf0:] = n
+
+
 def assemble_scene(meshes, box_and_angle, cat_ids, classes, colors=None, without_lamp: bool = False, floor: bool = False,
-                   degrees: bool = True, flip: bool = True) -> SceneMesh:
+                   degrees: bool = True, flip: bool = True, render_boxes: bool = False,
+                   tube_radius: float = 0.006) -> SceneMesh:
     """What render_v2_full hands to trimesh.Scene (visualize_scene.py:401, 433-436), as ONE mesh on the device: the shaped
     objects (neither `_scene_` nor `floor`; lamps left out when without_lamp) fitted into their boxes, in input order, then
     the floor quad when `floor` (the reference's `demo`).  meshes: a Meshes or the SDF batch of the shaped objects.
-    flip reverses the winding like pytorch3d_to_trimesh's invert(); degrees as get_generated_models_v2 (:320)."""
+    flip reverses the winding like pytorch3d_to_trimesh's invert(); degrees as get_generated_models_v2 (:320).
+    render_boxes: the tube markers of util.py:330-331 (radius 0.006, four sections) for EVERY shaped object -- a lamp's marker
+    stays in the scene under without_lamp, as there -- after all objects and before the floor."""
     meshes = _as_meshes(meshes)
+    sections, radius = _check_marker(4, tube_radius) if render_boxes else (4, 0.006)
     box7, cats, labels, shaped, node_col, lamps = _plan(box_and_angle, meshes, cat_ids, classes, colors, without_lamp)
     n = len(cats)
     keep = [(j in shaped) and (j not in lamps) for j in range(n)]
+    rows = _floor_rows(labels, "assemble_scene") if floor else None
+    mark = [j in shaped for j in range(n)] if render_boxes else None
     v, c, f, o, pts, _, kept, nv, nf = _assemble(meshes.verts_list(), meshes.faces_list(), shaped, box7, keep, node_col,
                                                  degrees, flip, extra_verts=4 if floor else 0,
-                                                 extra_faces=2 if floor else 0)
+                                                 extra_faces=2 if floor else 0, mark_nodes=mark, sections=sections,
+                                                 radius=radius)
     if floor:
-        rows = torch.tensor([j for j in range(n) if labels[j] != "_scene_"], dtype=torch.int64).to(v.device)
-        if rows.numel() == 0:
-            raise L.CsError("assemble_scene: no box besides _scene_ to span the floor")
-        bottom = pts[rows][:, [0, 1, 4, 5]]                                   # create_floor's corner rows
-        x0, x1, z0, z1 = bottom[..., 0].min(), bottom[..., 0].max(), bottom[..., 2].min(), bottom[..., 2].max()
-        zero = torch.zeros((), dtype=torch.float32, device=v.device)
-        nv0, nf0 = v.shape[0] - 4, f.shape[0] - 2
-        v[nv0:] = torch.stack([torch.stack([x0, zero, z0]), torch.stack([x0, zero, z1]), torch.stack([x1, zero, z1]),
-                               torch.stack([x1, zero, z0])])
-        c[nv0:] = torch.tensor(FLOOR_RGB, dtype=torch.float32, device=v.device)
-        f[nf0:] = torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int64, device=v.device) + nv0
-        o[nf0:] = n
+        _add_floor(v, c, f, o, pts, rows, n)
         kept, nv, nf = kept + [n], nv + [4], nf + [2]
     return SceneMesh(v, f, c, o, pts, kept, nv, nf)
+
+
+# ---------------------------------------------------------------- scenes from a mesh library (csrc/cs_scene_lib.hip)
+RENDER_TYPES = ("retrieval", "library", "onlybox")
+# the marker radii of the reference: util.py:135 (retrieval), :374 (get_sdfusion_models: create_bbox_marker's default), :149
+MARKER_RADIUS = {"retrieval": 0.006, "library": 0.002, "onlybox": 0.02}
+
+
+def get_closest_furniture_to_box(box_dict, query_size) -> str:
+    """helpers/util.py:71-83 for ONE query through cs_scene_retrieve: box_dict {model id: (l, h, w)} in its own order, query_size
+    three numbers (a tensor row, rounded to fp32 like the box tensor it comes from) -> the id of the first closest model"""
+    from .scene_library import FurnitureLibrary
+    if not hasattr(box_dict, "items") or len(box_dict) == 0:
+        raise L.CsError("get_closest_furniture_to_box: box_dict must be a non-empty {id: (l, h, w)}")
+    q = torch.as_tensor(query_size).detach().reshape(-1)
+    if q.numel() != 3:
+        raise L.CsError(f"get_closest_furniture_to_box: query_size must hold (l, h, w), got {q.numel()} numbers")
+    lib = FurnitureLibrary({"_": list(box_dict.items())}, what="get_closest_furniture_to_box")
+    rows, _, status = lib.retrieve_rows(q.reshape(1, 3), [0])
+    lib._raise_refused(rows.cpu().tolist(), status.cpu().tolist(), ["query"], "get_closest_furniture_to_box")
+    return lib.ids[int(rows.item())]
+
+
+def choose_shape_files(labels: Sequence[str], library, no_stool: bool = False, rng=None) -> List[str]:
+    """The draws of get_sdfusion_models (util.py:351-358) for the shaped objects `labels`, in its order: a = randint(0, 100);
+    seed(a); choice(files of the label); for a chair under no_stool: choice(stool files), then choice of the two.  Draws on
+    Python's `random` module, or on the random.Random passed as rng.  Host work only.  `library.category(label)` is the sorted
+    file list (the reference's is in glob order)."""
+    import random as _random
+    r = _random if rng is None else rng
+    files = {lab: library.category(lab) for lab in set(labels)}          # a missing folder raises before any draw
+    if no_stool and "chair" in files:
+        files["stool"] = library.category("stool")
+    out = []
+    for lab in labels:
+        a = r.randint(0, 100)
+        r.seed(a)
+        path = r.choice(files[lab])
+        if no_stool and lab == "chair":
+            path2 = r.choice(files["stool"])
+            path = r.choice([path, path2])
+        out.append(path)
+    return out
+
+
+def _library_plan(render_type: str, boxes, cat_ids, classes, library, sections, radius, no_stool: bool, rng):
+    """every argument check of the library scenes, then the host-side choices that need no device (the library type's draws)"""
+    from .scene_library import FurnitureLibrary, ShapeLibrary
+    if render_type not in RENDER_TYPES:
+        raise L.CsError(f"scene_mesh: render_type must be one of {RENDER_TYPES}, got {render_type!r}")
+    sections, radius = _check_marker(sections, MARKER_RADIUS[render_type] if radius is None else radius)
+    shape = tuple(torch.as_tensor(boxes).shape)
+    cats = _check_inputs(shape[0] if shape else 0, shape, cat_ids, classes)
+    labels = [_label(classes, c) for c in cats]
+    shaped = [j for j, lab in enumerate(labels) if not _skipped(lab)]
+    files = None
+    if render_type == "retrieval":
+        if not isinstance(library, FurnitureLibrary):
+            raise L.CsError("scene_mesh: render_type 'retrieval' needs a scene_library.FurnitureLibrary as `library`")
+        for j in shaped:
+            if labels[j] not in library.label_index:
+                raise L.CsError(f"scene_mesh: box {j} ({labels[j]!r}): the library has no such category")
+    elif render_type == "library":
+        if not isinstance(library, ShapeLibrary):
+            raise L.CsError("scene_mesh: render_type 'library' needs a scene_library.ShapeLibrary as `library`")
+        files = choose_shape_files([labels[j] for j in shaped], library, no_stool, rng)
+    return sections, radius, cats, labels, shaped, files
+
+
+def _library_scene(render_type: str, boxes, cat_ids, classes, library, colors, without_lamp: bool, render_boxes: bool,
+                   radius, sections, floor: bool, no_stool: bool, rng):
+    """-> (SceneMesh, plan): the one device path behind the list-returning functions and assemble_scene_from_library"""
+    sections, radius, cats, labels, shaped, files = _library_plan(render_type, boxes, cat_ids, classes, library, sections,
+                                                                  radius, no_stool, rng)
+    rows = _floor_rows(labels, "assemble_scene_from_library") if floor else None
+    box7, cats, labels, shaped, node_col, lamps = _plan_nodes(boxes, None, cat_ids, classes, colors, without_lamp)
+    n = len(cats)
+    verts, faces, sources = [], [], []
+    if render_type == "retrieval" and shaped:
+        idx = torch.tensor(shaped, dtype=torch.int64).to(box7.device)
+        lib_rows, _, status = library.retrieve_rows(box7[idx], [library.label_index[labels[j]] for j in shaped])
+        lib_rows, status = lib_rows.cpu().tolist(), status.cpu().tolist()      # the one read-back: which meshes to place
+        library._raise_refused(lib_rows, status, [labels[j] for j in shaped], "scene_mesh", numbers=shaped)
+        for r in lib_rows:
+            v, f = library.mesh(r)
+            verts.append(v)
+            faces.append(f)
+            sources.append(library.ids[r])
+    elif render_type == "library":
+        for path in files:
+            v, f = library.mesh(path)
+            verts.append(v)
+            faces.append(f)
+            sources.append(path)
+    marks_on = render_boxes or render_type == "onlybox"
+    if render_type == "onlybox":
+        keep = [False] * n                                  # get_bbox: a lamp's marker itself leaves the scene (:152-153)
+        mark = [(j in shaped) and (j not in lamps) for j in range(n)]
+        node_of_mesh = []
+    else:
+        keep = [(j in shaped) and (j not in lamps) for j in range(n)]
+        mark = [j in shaped for j in range(n)] if marks_on else None     # (:131-135, :370-374: a lamp's marker stays)
+        node_of_mesh = shaped
+    # retrieval places (no scale, no inversion); the library type inverts and fits like the generated shapes (:361, :368)
+    v, c, f, o, pts, _, kept, nv, nf = _assemble(verts, faces, node_of_mesh, box7, keep, node_col, degrees=True,
+                                                 flip=render_type == "library", extra_verts=4 if floor else 0,
+                                                 extra_faces=2 if floor else 0, placed=render_type != "library",
+                                                 mark_nodes=mark, sections=sections, radius=radius)
+    if floor:
+        _add_floor(v, c, f, o, pts, rows, n)
+        kept, nv, nf = kept + [n], nv + [4], nf + [2]
+    kept_src = [sources[shaped.index(j)] for j in kept[:sum(keep)]] if sources else []
+    scene = SceneMesh(v, f, c, o, pts, kept, nv, nf, kept_src)
+    return scene, dict(cats=cats, labels=labels, shaped=shaped, lamps=lamps, verts=verts, faces=faces, sources=sources,
+                       n_objects=sum(keep), node_col=node_col, keep=keep, mark=mark)
+
+
+def assemble_scene_from_library(render_type: str, box_and_angle, cat_ids, classes, library=None, colors=None,
+                                without_lamp: bool = False, render_boxes: bool = False, tube_radius: Optional[float] = None,
+                                sections: int = 4, floor: bool = False, no_stool: bool = False, rng=None) -> SceneMesh:
+    """The layout-only scenes of visualize_scene.py:208-461 as ONE mesh on the device.  render_type:
+      retrieval  per box the closest model of a FurnitureLibrary, placed (util.py:86-138);
+      library    per box a drawn shape of a ShapeLibrary, inverted and fitted (get_sdfusion_models, :335-376);
+      onlybox    tube markers only (get_bbox, :140-156; render_boxes is implied).
+    Content: the kept objects in input order, then the markers in input order, then the floor when asked.  tube_radius
+    defaults to the reference's per type (0.006 / 0.002 / 0.02).  `scene.sources` names the model / file of each kept object.
+    without_lamp: a lamp's mesh leaves the scene; its marker stays for retrieval / library and leaves for onlybox."""
+    return _library_scene(render_type, box_and_angle, cat_ids, classes, library, colors, without_lamp, render_boxes,
+                          tube_radius, sections, floor, no_stool, rng)[0]
+
+
+def _lists_from_scene(scene: SceneMesh, plan: dict):
+    """the reference's return lists from one assembled scene: objects and markers interleaved per box, lamps apart"""
+    parts = scene.per_object()
+    nobj = plan["n_objects"]
+    obj_of = {j: parts[k] for k, j in enumerate(scene.kept[:nobj])}
+    mark_of = {j: parts[nobj + k] for k, j in enumerate(scene.kept[nobj:])}
+    lamp_list, out = [], []
+    for j in plan["shaped"]:
+        if j in obj_of:
+            (lamp_list if j in plan["lamps"] else out).append(obj_of[j])
+        if j in mark_of:
+            out.append(mark_of[j])
+    return lamp_list, out
+
+
+def _raw_meshes(plan: dict, flip: bool, mesh_dir) -> List[TriMesh]:
+    raw = []
+    if mesh_dir is not None:
+        os.makedirs(mesh_dir, exist_ok=True)
+    for k, j in enumerate(plan["shaped"]):
+        v, f = plan["verts"][k], plan["faces"][k]
+        col = torch.from_numpy(plan["node_col"][j].astype(np.float32)).to(v.device).expand(v.shape[0], 3)
+        raw.append(TriMesh(v, torch.flip(f, dims=[1]) if flip else f, col))
+        if mesh_dir is not None:
+            raw[-1].export(os.path.join(mesh_dir, f"{plan['labels'][j]}_{plan['cats'][j]}_{k + 1}.obj"))
+    return raw
+
+
+def get_textured_objects_v2(boxes, library, cat_ids, classes, mesh_dir=None, render_boxes: bool = False, colors=None,
+                            without_lamp: bool = False):
+    """helpers/util.py:86-138 -> (lamp_mesh_list, trimesh_meshes, raw_meshes) of TriMesh.  `library` (a FurnitureLibrary)
+    replaces the reference's `datasize`, which selects two hard-coded paths.  The placed models in input order, each followed
+    by its marker (radius 0.006) when render_boxes; a lamp's model goes to the lamp list under without_lamp, its marker stays."""
+    scene, plan = _library_scene("retrieval", boxes, cat_ids, classes, library, colors, False, render_boxes, None, 4,
+                                 False, False, None)
+    plan["lamps"] = [j for j in plan["shaped"] if plan["labels"][j] == "lamp" and without_lamp]
+    lamp_list, out = _lists_from_scene(scene, plan)
+    return lamp_list, out, _raw_meshes(plan, False, mesh_dir)
+
+
+def get_bbox(boxes, cat_ids, classes, colors=None, without_lamp: bool = False):
+    """helpers/util.py:140-156 -> (lamp_mesh_list, trimesh_meshes): one marker (radius 0.02) per shaped box; under without_lamp a
+    lamp's marker goes to the lamp list"""
+    scene, plan = _library_scene("onlybox", boxes, cat_ids, classes, None, colors, False, True, None, 4, False, False, None)
+    lamp_list, out = [], []
+    for j, m in zip(scene.kept, scene.per_object()):
+        (lamp_list if (plan["labels"][j] == "lamp" and without_lamp) else out).append(m)
+    return lamp_list, out
+
+
+def get_sdfusion_models(boxes, library, cat_ids, classes, mesh_dir=None, render_boxes: bool = False, colors=None,
+                        no_stool: bool = False, without_lamp: bool = False, rng=None):
+    """helpers/util.py:335-376 -> (lamp_mesh_list, obj_list, raw_obj_list).  `library` (a ShapeLibrary) replaces the hard-coded
+    folder.  Per shaped object the reference's own draws in its order (`choose_shape_files`), then invert and fit: the
+    cs_scene_fit_boxes / cs_scene_apply path with flip, as for generated shapes.  Markers have radius 0.002 (:374)."""
+    scene, plan = _library_scene("library", boxes, cat_ids, classes, library, colors, False, render_boxes, None, 4, False,
+                                 no_stool, rng)
+    plan["lamps"] = [j for j in plan["shaped"] if plan["labels"][j] == "lamp" and without_lamp]
+    lamp_list, out = _lists_from_scene(scene, plan)
+    return lamp_list, out, _raw_meshes(plan, True, mesh_dir)
+
+
+def create_bbox_marker(corner_points, color=(0, 0, 255), tube_radius: float = 0.002, sections: int = 4) -> TriMesh:
+    """helpers/util.py:393-421: twelve tubes along the edges of the box with corners corner_points [8,3] (in
+    params_to_8points_3dfront's order) -> TriMesh of 12 (2 sections + 2) vertices and 48 sections faces, closed and wound
+    outward per tube (the layout is documented in include/commonscenes_hip.h).  color: 0..255 integers or 0..1 floats."""
+    sections, radius = _check_marker(sections, tube_radius)
+    pts = torch.as_tensor(corner_points)
+    if tuple(pts.shape) != (8, 3):
+        raise L.CsError(f"create_bbox_marker: corner_points must be [8, 3], got {tuple(pts.shape)}")
+    col = np.asarray(color)
+    if col.size < 3:
+        raise L.CsError(f"create_bbox_marker: color must hold r, g, b, got {color!r}")
+    col = (col.astype(np.float64) / 255.0 if np.issubdtype(col.dtype, np.integer) else col.astype(np.float64)).reshape(-1)[:3]
+    dev = _device()
+    pts = pts.detach().to(device=dev, dtype=torch.float32).contiguous().view(1, 8, 3)
+    nv, nf = 12 * (2 * sections + 2), 48 * sections
+    out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    out_c = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+    out_o = torch.empty((nf,), dtype=torch.int32, device=dev)
+    zero = torch.zeros((1,), dtype=torch.int64, device=dev)
+    keep = torch.ones((1,), dtype=torch.bool, device=dev)
+    c = torch.from_numpy(col.astype(np.float32)).to(dev).view(1, 3)
+    L.check(L.load().cs_scene_box_markers(pts.data_ptr(), 1, keep.data_ptr(), zero.data_ptr(), zero.data_ptr(), c.data_ptr(),
+                                          sections, radius, out_v.data_ptr(), out_c.data_ptr(), nv, out_f.data_ptr(),
+                                          out_o.data_ptr(), nf, _stream()), "cs_scene_box_markers")
+    return TriMesh(out_v, out_f, out_c)
 
 
 def render_topdown(scene: SceneMesh, size: int = 256) -> dict:

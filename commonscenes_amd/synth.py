@@ -190,3 +190,65 @@ def iou_case(thres: float):
     b[0, 0, 40, 41, 42] = float(np.float32(thres))
     b[2] += float(np.float32(max(thres, 0.0)))          # stays free for every threshold
     return a, b
+
+
+def _box_mesh(size):
+    """an axis-aligned box of (l, h, w) standing on y = 0, centred in x / z: 8 vertices, 12 outward triangles"""
+    l, h, w = [float(s) for s in size]
+    v = np.asarray([[l / 2 * i, h * j, w / 2 * k] for i in (-1, 1) for j in (0, 1) for k in (-1, 1)], dtype=np.float32)
+    f = np.asarray([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6], [0, 2, 6], [0, 6, 4],
+                    [1, 5, 7], [1, 7, 3]], dtype=np.int64)
+    return torch.from_numpy(v), torch.from_numpy(f)
+
+
+def _ellipsoid_mesh(size, rings: int = 6, segments: int = 8):
+    """an ellipsoid inscribed in the same box: a latitude / longitude mesh, poles on the y axis"""
+    l, h, w = [float(s) for s in size]
+    vs = [[0.0, 0.0, 0.0]]
+    for r in range(1, rings):
+        th = np.pi * r / rings
+        for s in range(segments):
+            ph = 2 * np.pi * s / segments
+            vs.append([l / 2 * np.sin(th) * np.cos(ph), h / 2 - h / 2 * np.cos(th), w / 2 * np.sin(th) * np.sin(ph)])
+    vs.append([0.0, h, 0.0])
+    top = len(vs) - 1
+    ring = lambda r, s: 1 + (r - 1) * segments + s % segments
+    fs = []
+    for s in range(segments):
+        fs.append([0, ring(1, s), ring(1, s + 1)])
+        fs.append([top, ring(rings - 1, s + 1), ring(rings - 1, s)])
+        for r in range(1, rings - 1):
+            fs.append([ring(r, s), ring(r + 1, s), ring(r + 1, s + 1)])
+            fs.append([ring(r, s), ring(r + 1, s + 1), ring(r, s + 1)])
+    return torch.from_numpy(np.asarray(vs, dtype=np.float32)), torch.from_numpy(np.asarray(fs, dtype=np.int64))
+
+
+def furniture_table(labels, per_category: int = 8, seed: int = 111):
+    """A small synthetic furniture library (3D-FUTURE is not reachable offline): per label `per_category` models,
+    alternately boxes and ellipsoids, sizes hash-uniform in [0.2, 2.2) -> {label: [(id, (l, h, w), verts, faces), ...]}, the
+    argument of scene_library.FurnitureLibrary.from_meshes."""
+    table = OrderedDict()
+    for lab in labels:
+        lab = lab.strip("\n")
+        sz = hash_uniform(f"furniture:{lab}", per_category * 3, seed).reshape(per_category, 3) + 1.2
+        table[lab] = []
+        for k in range(per_category):
+            size = [float(np.float32(x)) for x in sz[k]]
+            v, f = _box_mesh(size) if k % 2 == 0 else _ellipsoid_mesh(size)
+            table[lab].append((f"{lab}-{k:03d}", size, v, f))
+    return table
+
+
+def furniture_library(labels, per_category: int = 8, seed: int = 111):
+    from .scene_library import FurnitureLibrary
+    return FurnitureLibrary.from_meshes(furniture_table(labels, per_category, seed))
+
+
+def write_shape_library(root, labels, per_category: int = 4, seed: int = 111) -> None:
+    """the same models as `root/<label>/<id>.ply`: the folder layout scene_library.ShapeLibrary reads"""
+    import os
+    from .scene_library import write_ply
+    for lab, entries in furniture_table(labels, per_category, seed).items():
+        os.makedirs(os.path.join(root, lab), exist_ok=True)
+        for mid, _, v, f in entries:
+            write_ply(os.path.join(root, lab, mid + ".ply"), v, f, binary=True)

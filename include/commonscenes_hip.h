@@ -1306,6 +1306,51 @@ int cs_mesh_sdf_grid(const float* tris, int64_t total_faces, const int64_t* meta
 int cs_mesh_sdf_finish(const void* ws, int64_t ws_bytes, const int64_t* meta, int nb, int n, int use_sign, float wind_level,
                        float trunc, float* out, float* wout, cs_stream_t stream);
 
+/*
+ * Scenes from a mesh library (csrc/cs_scene_lib.hip): the retrieval, txt2shape-library and boxes-only render types of
+ * helpers/visualize_scene.py:208-461 (helpers/util.py:71-156, :335-421).  Additions to ABI 18.  The meshes themselves go through
+ * cs_scene_fit_boxes / cs_scene_apply / cs_scene_raster_topdown / cs_scene_resolve unchanged.  Every buffer is caller-owned
+ * device memory; nothing synchronises; no LDS, no atomics: an answer is a function of its own box only.
+ *
+ * cs_scene_retrieve: get_closest_furniture_to_box (util.py:71-83) for nq boxes.  sizes fp64 [m][3] = the library's (l, h, w)
+ *   rows; cat_base int64 [ncat + 1] = CSR over those rows (category c owns rows cat_base[c] .. cat_base[c + 1] - 1); query i is
+ *   columns 0..2 of boxes + i * ld (fp32, ld >= 3 in floats) and query_cat[i] (int32).  In numpy's promotion and order:
+ *     d = size - (double)query per component;  d2 = ((d0 d0 + d1 d1) + d2 d2);  index[i] = the row of the smallest d2, the
+ *   lowest such row among equals (np.argmin's first minimum); d2[i] that value (fp64).  One wave per query.
+ *   status int32 [nq] is written (not OR-ed): CS_RETRIEVE_STATUS_NONFINITE a query size that is not finite, _CATEGORY a
+ *   category id outside 0..ncat-1, _EMPTY a category without rows (or a CSR range that leaves 0..m), _NODISTANCE every
+ *   distance of the category overflowed.  Such a query gets index -1 and d2 +inf; the others are answered.
+ * cs_scene_place_boxes: n boxes [n][7] fp32 (l, h, w, px, py, pz, angle; degrees if `degrees`), one thread per box, fp64,
+ *   rounded once -> xform [n][12] fp32 = retrieval's placement (util.py:121-129, vertices.dot(R) + t, neither scaled nor
+ *   inverted) as the row-major 3x4 map cs_scene_apply consumes: {c, 0, s, tx}, {0, 1, 0, ty}, {-s, 0, c, tz};
+ *   box_points [n][8][3] fp32 = the corners, bit-equal to cs_scene_fit_boxes' for the same boxes.
+ * cs_scene_box_markers: create_bbox_marker (util.py:393-421) for the boxes with keep[i] != 0, written into the scene buffers of
+ *   cs_scene_apply: box i owns 12 (2 S + 2) vertices from out_vert_base[i] and 48 S faces from out_face_base[i] (S =
+ *   sections), tube e of the edge table of util.py:405 at e (2 S + 2) / e 4 S inside them; faces carry scene-global vertex
+ *   ids, face_object = i, out_rgb = color[i] ([n][3] fp32).  box_points is read on the device.  A box whose range leaves the
+ *   buffers is skipped whole.  trimesh.creation.cylinder's vertex order cannot be pinned without trimesh, so the tube is
+ *   this library's: for the edge (a, b) in fp64, d = b - a; m = the axis of the smallest |d_m| (lowest index on ties);
+ *   u = normalize(d x e_m); w = (d / |d|) x u; ring vertex k of end j (0 = a, 1 = b) = p_j + r (cos(2 pi k / S) u +
+ *   sin(2 pi k / S) w) at j S + k, the cap centres a, b at 2 S and 2 S + 1; each rounded once to fp32.  Faces, wound outward:
+ *   f in [0, S): (a_k, a_k+1, b_k+1); [S, 2S): (a_k, b_k+1, b_k); [2S, 3S): (centre a, a_k+1, a_k); [3S, 4S): (centre b, b_k,
+ *   b_k+1), k = f mod S, k + 1 mod S.  An edge of zero or non-finite length puts every vertex on a: counts stay, faces have no
+ *   area.  radius is the fp32 value, widened.
+ * CS_EINVAL for NULL pointers, m / ncat / nq / n < 1, ld < 3, sections outside 3..64, a radius that is not positive and finite.
+ */
+#define CS_RETRIEVE_STATUS_NONFINITE 1
+#define CS_RETRIEVE_STATUS_CATEGORY 2
+#define CS_RETRIEVE_STATUS_EMPTY 4
+#define CS_RETRIEVE_STATUS_NODISTANCE 8
+#define CS_MARKER_MIN_SECTIONS 3
+#define CS_MARKER_MAX_SECTIONS 64
+int cs_scene_retrieve(const double* sizes, int64_t m, const int64_t* cat_base, int ncat, const float* boxes, int64_t ld,
+                      const int32_t* query_cat, int64_t nq, int64_t* index, double* d2, int32_t* status, cs_stream_t stream);
+int cs_scene_place_boxes(const float* box7, int64_t n, int degrees, float* xform, float* box_points, cs_stream_t stream);
+int cs_scene_box_markers(const float* box_points, int64_t n, const uint8_t* keep, const int64_t* out_vert_base,
+                         const int64_t* out_face_base, const float* color, int sections, float radius, float* out_verts,
+                         float* out_rgb, int64_t out_nverts, int64_t* out_faces, int32_t* face_object, int64_t out_nfaces,
+                         cs_stream_t stream);
+
 /* Library / device self-description. */
 int cs_abi_version(void);
 

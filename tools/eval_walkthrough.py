@@ -107,7 +107,72 @@ def build_experiment(tmp: Path, width: int):
     return opt
 
 
-def export_scene(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs):
+def open_library(spec, render_type, classes, tmp):
+    """--library: `synthetic` (commonscenes_amd.synth: boxes and ellipsoids per class, nothing on disk but a temporary folder
+    for the `library` type), `JSON MODEL_ROOT` (cat_jid_trainval*.json + the 3D-FUTURE model folder) or `DIR` (label folders of
+    *.ply / *.obj) -> the FurnitureLibrary (retrieval) or ShapeLibrary (library) the render type needs; None for onlybox"""
+    from commonscenes_amd import scene_library as SL, synth
+    if render_type in ("generated", "onlybox"):
+        return None
+    if not spec:
+        raise SystemExit(f"--render-type {render_type} needs --library")
+    labels = [c for c in classes if c.strip() not in ("_scene_", "floor")]
+    if render_type == "retrieval":
+        if spec == ["synthetic"]:
+            return synth.furniture_library(labels)
+        if len(spec) != 2:
+            raise SystemExit("--render-type retrieval needs --library synthetic or --library JSON MODEL_ROOT")
+        return SL.FurnitureLibrary.from_json(spec[0], spec[1])
+    if spec == ["synthetic"]:
+        synth.write_shape_library(str(tmp / "shape_library"), labels)
+        return SL.ShapeLibrary(tmp / "shape_library")
+    if len(spec) != 1:
+        raise SystemExit("--render-type library needs --library synthetic or --library DIR")
+    return SL.ShapeLibrary(spec[0])
+
+
+def export_layout_scene(out_dir, scan, render_type, render_boxes, library, boxes_pred, angles_pred, dec_objs):
+    """--export-scenes with --render-type retrieval | library | onlybox: the scene from the mesh library (no generated
+    shapes: the v2_box use) and its top-down view -> DIR/<scan>.obj, DIR/<scan>.png"""
+    import random
+    from commonscenes_amd import scene_mesh as S
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    classes = list(VOCAB["object_idx_to_name"])
+    classes[0], classes[-1] = "_scene_\n", "floor\n"
+    box_and_angle = torch.cat([boxes_pred.float(), angles_pred.float()], dim=1)
+    cats = dec_objs.cpu().tolist()
+    times = {}
+    for tag in ("first_call_s", "device_s"):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        scene = S.assemble_scene_from_library(render_type, box_and_angle, cats, classes, library=library,
+                                              render_boxes=render_boxes, floor=True, rng=random.Random(48))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        img = S.render_topdown(scene, 256)
+        torch.cuda.synchronize()
+        times[tag] = time.perf_counter() - t0
+        times["assemble_s"], times["render_s"] = t1 - t0, time.perf_counter() - t1
+    scene.export_obj(out / f"{scan}.obj")
+    image = _save_image(out, scan, img["rgb"].cpu().numpy())
+    return dict(obj=f"{scan}.obj", image=image, verts=int(scene.verts.shape[0]), faces=int(scene.faces.shape[0]),
+                dropped=img["dropped"], covered=int((img["object_id"] >= 0).sum()), render_type=render_type,
+                render_boxes=bool(render_boxes or render_type == "onlybox"),
+                sources=[os.path.basename(str(x)) for x in scene.sources], **times)
+
+
+def _save_image(out, scan, rgb):
+    try:
+        from PIL import Image
+        Image.fromarray(rgb).save(out / f"{scan}.png")
+        return f"{scan}.png"
+    except ImportError:
+        np.save(out / f"{scan}.npy", rgb)
+        return f"{scan}.npy"
+
+
+def export_scene(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs, render_boxes=False):
     """--export-scenes: the scene mesh and its top-down view, timed on the device (second call: the first loads the code
     objects), and the host numpy restatement of fit_shapes_to_box_v2 over the same meshes for context."""
     from commonscenes_amd import scene_mesh as S
@@ -121,7 +186,7 @@ def export_scene(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs):
     for tag in ("first_call_s", "device_s"):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        scene = S.assemble_scene(meshes, box_and_angle, cats, classes, floor=True)
+        scene = S.assemble_scene(meshes, box_and_angle, cats, classes, floor=True, render_boxes=render_boxes)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         img = S.render_topdown(scene, 256)
@@ -147,14 +212,7 @@ def export_scene(out_dir, scan, meshes, boxes_pred, angles_pred, dec_objs):
             (v1 / size * np.array([l, h, w])).dot(np.linalg.inv(rot).T) + np.array([px, py, pz])
     times["numpy_fit_s"] = time.perf_counter() - t0
     scene.export_obj(out / f"{scan}.obj")
-    rgb = img["rgb"].cpu().numpy()
-    try:
-        from PIL import Image
-        Image.fromarray(rgb).save(out / f"{scan}.png")
-        image = f"{scan}.png"
-    except ImportError:
-        np.save(out / f"{scan}.npy", rgb)
-        image = f"{scan}.npy"
+    image = _save_image(out, scan, img["rgb"].cpu().numpy())
     nv, nf = int(scene.verts.shape[0]), int(scene.faces.shape[0])
     # cs_scene_apply reads 12 B per vertex and 24 B per face, writes 24 B per vertex (position + colour) and 28 B per face
     return dict(obj=f"{scan}.obj", image=image, verts=nv, faces=nf, dropped=img["dropped"],
@@ -206,6 +264,16 @@ def main():
                          "hands to trimesh.Scene, helpers/visualize_scene.py:401-436) and render its 256x256 top-down view "
                          "(render_img, :85-116); writes DIR/<scan>.obj and DIR/<scan>.png (.npy without PIL) and reports the "
                          "device time next to a host numpy restatement of the fit (helpers/util.py:158-189)")
+    ap.add_argument("--render-type", choices=["generated", "retrieval", "library", "onlybox"], default="generated",
+                    help="with --export-scenes DIR: what fills the boxes (helpers/visualize_scene.py:208-461): the generated shapes "
+                         "(default), the closest model of a furniture library, a drawn shape of a shape library, or tube "
+                         "markers only.  With retrieval / library / onlybox the shape branch is not sampled (the v2_box use) "
+                         "and only the layout scenes are exported")
+    ap.add_argument("--render-boxes", action="store_true",
+                    help="with --export-scenes DIR: add tube markers along the box edges (helpers/util.py:393-421)")
+    ap.add_argument("--library", nargs="+", metavar="SPEC", default=None,
+                    help="the mesh library of --render-type retrieval / library: `synthetic`, `JSON MODEL_ROOT` "
+                         "(cat_jid_trainval*.json and the model folder; retrieval) or `DIR` (label folders of *.ply; library)")
     ap.add_argument("--object-views", action="store_true",
                     help="with --export-scenes DIR: additionally render every shaped object on its own (object_views: the "
                          "reference's init_mesh_renderer(256, 1.7, 20, 20) + get_current_visuals_v2) and write "
@@ -220,6 +288,10 @@ def main():
     a = ap.parse_args()
     if a.object_views and not a.export_scenes:
         ap.error("--object-views needs --export-scenes DIR")
+    if (a.render_type != "generated" or a.render_boxes) and not a.export_scenes:
+        ap.error("--render-type / --render-boxes need --export-scenes DIR")
+    if a.render_type != "generated" and a.object_views:
+        ap.error("--object-views renders generated shapes: not with --render-type " + a.render_type)
     if a.diversity_gpu and a.samples < 2:
         ap.error("--diversity-gpu needs at least two runs per object (--samples)")
 
@@ -250,6 +322,39 @@ def main():
         model.compute_statistics(str(tmp), 100, synthetic_loader(3, seed=900))
         model.eval()
         loader = synthetic_loader(a.scenes, seed=500, objects=a.objects)
+        if a.render_type != "generated":                      # layout only: boxes and angles, no sampler step
+            classes = list(VOCAB["object_idx_to_name"])
+            classes[0], classes[-1] = "_scene_\n", "floor\n"
+            library = open_library(a.library, a.render_type, classes, tmp)
+            calls = [0]
+            rel2shape = model.vae_v2.Diff.rel2shape
+
+            def counted(*args, **kw):
+                calls[0] += 1
+                return rel2shape(*args, **kw)
+            model.vae_v2.Diff.rel2shape = counted
+            t_all = time.perf_counter()
+            for data in loader:
+                d = data["decoder"]
+                dec_objs = d["objs"].cuda()
+                with torch.no_grad():
+                    (boxes_pred, angles_pred), shapes = model.sample_box_and_shape(
+                        None, dec_objs, d["tripltes"].cuda(), d["sdfs"], d["text_feats"].cuda(), d["rel_feats"].cuda(),
+                        attributes=None, gen_shape=False)
+                angles_pred = -180 + (torch.argmax(angles_pred, dim=1, keepdim=True) + 1) * 15.0
+                assert shapes is None
+                export = export_layout_scene(a.export_scenes, data["scan_id"][0], a.render_type, a.render_boxes, library,
+                                             boxes_pred, angles_pred, dec_objs) if rank == 0 else None
+                res["scenes"].append(dict(scan=data["scan_id"][0], nodes=int(dec_objs.shape[0]), shapes=0,
+                                          finite=bool(torch.isfinite(boxes_pred).all()), export=export))
+            torch.cuda.synchronize()
+            res.update(total_s=time.perf_counter() - t_all, render_type=a.render_type, sampler_calls=calls[0])
+            if rank == 0:
+                print("EVAL_WALKTHROUGH " + json.dumps(res), flush=True)
+            if world > 1:
+                torch.distributed.barrier()
+                torch.distributed.destroy_process_group()
+            return
         if a.compare_attention:
             from commonscenes_amd import synth
             d = loader[0]["decoder"]
@@ -347,8 +452,8 @@ def main():
             torch.cuda.synchronize()
             t_scene = time.perf_counter() - t0
             nshape = shapes_pred.shape[0]
-            export = export_scene(a.export_scenes, data["scan_id"][0], meshes, boxes_pred, angles_pred, dec_objs) \
-                if a.export_scenes and rank == 0 else None
+            export = export_scene(a.export_scenes, data["scan_id"][0], meshes, boxes_pred, angles_pred, dec_objs,
+                                  a.render_boxes) if a.export_scenes and rank == 0 else None
             if a.object_views and rank == 0:
                 n_img, t_r, t_w = export_object_views(a.export_scenes, data["scan_id"][0], meshes, boxes_pred, angles_pred,
                                                        dec_objs, view_renderer)

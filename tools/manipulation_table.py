@@ -79,8 +79,12 @@ def build_model(W, tmp: Path, width: int):
     return model.eval()
 
 
-def export_edit(out_dir, model, edit, names, ddim_steps, shape_nodes, seed):
-    """<scan>_before.obj / .png and <scan>_after_<label>.obj / .png (.npy without PIL)"""
+def export_edit(out_dir, model, edit, names, ddim_steps, shape_nodes, seed, render_type="generated", render_boxes=False,
+                library=None):
+    """<scan>_before.obj / .png and <scan>_after_<label>.obj / .png (.npy without PIL).  render_type retrieval / library /
+    onlybox fills the edited layout from the mesh library instead of the generated shapes (scene_mesh.
+    assemble_scene_from_library); render_boxes adds the tube markers."""
+    import random
     from commonscenes_amd import manipulation as MP, scene_mesh as S
     out = Path(out_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -93,7 +97,11 @@ def export_edit(out_dir, model, edit, names, ddim_steps, shape_nodes, seed):
     label = names[res["after"][2][res["changed"][0]]].strip() if res["changed"] else "none"
     files = []
     for tag, (meshes, boxes, cats) in (("before", res["before"]), (f"after_{label}", res["after"])):
-        scene = S.assemble_scene(meshes, boxes, cats, names, floor=True)
+        if render_type == "generated":
+            scene = S.assemble_scene(meshes, boxes, cats, names, floor=True, render_boxes=render_boxes)
+        else:
+            scene = S.assemble_scene_from_library(render_type, boxes, cats, names, library=library, render_boxes=render_boxes,
+                                                  floor=True, rng=random.Random(seed))
         img = S.render_topdown(scene, 256)
         scene.export_obj(out / f"{scan}_{tag}.obj")
         rgb = img["rgb"].cpu().numpy()
@@ -121,10 +129,17 @@ def main():
     ap.add_argument("--points", type=int, default=5000)
     ap.add_argument("--objects", type=int, default=None, help="shaped objects per scene (default 4, 5, ...)")
     ap.add_argument("--export-scenes", metavar="DIR", default=None)
+    ap.add_argument("--render-type", choices=["generated", "retrieval", "library", "onlybox"], default="generated",
+                    help="with --export-scenes: what fills the boxes of the before / after scenes (default: the generated shapes)")
+    ap.add_argument("--render-boxes", action="store_true", help="with --export-scenes: add tube markers along the box edges")
+    ap.add_argument("--library", nargs="+", metavar="SPEC", default=None,
+                    help="the mesh library of --render-type retrieval / library: `synthetic`, `JSON MODEL_ROOT` or `DIR`")
     ap.add_argument("--compare-sequential", action="store_true")
     a = ap.parse_args()
     if not a.synthetic:
         ap.error("only --synthetic is available: the real dataset and its CLIP features are not reachable offline")
+    if (a.render_type != "generated" or a.render_boxes) and not a.export_scenes:
+        ap.error("--render-type / --render-boxes need --export-scenes DIR")
     torch.cuda.set_device(0)
     from commonscenes_amd import manipulation as MP
     W = _walkthrough()
@@ -162,8 +177,12 @@ def main():
                 note="whole loop (encode, 1 + K decodes per scene, meshing, resampling, Chamfer, tables): one `_many` call "
                      "per batch of scenes vs one facade call per decode; report-only")
         if a.export_scenes:
-            res["export"] = [export_edit(a.export_scenes, model, e, names, a.ddim_steps, a.shape_nodes, 48 + i)
+            library = W.open_library(a.library, a.render_type, names, Path(td))
+            res["export"] = [export_edit(a.export_scenes, model, e, names, a.ddim_steps, a.shape_nodes, 48 + i,
+                                         a.render_type, a.render_boxes, library)
                              for i, e in enumerate(edits) if e is not None]
+            if a.render_type != "generated" or a.render_boxes:
+                res["export_render"] = dict(render_type=a.render_type, render_boxes=a.render_boxes)
     print("MANIPULATION_TABLE " + json.dumps(res), flush=True)
 
 
